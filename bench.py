@@ -1,18 +1,31 @@
 """Headline benchmark (BASELINE.json): samples/sec of ResNet-50 DDP training on 1..8 MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--model resnet50|gpt2_small]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds every secondary
+measurement after the timed region: the plain single-GPU step and BASELINE configs 4 / 5 in child processes
+(``plain_step_1gpu``, ``extra_configs``), the per-bucket communication timing of the ``comm`` block and, at
+N > 1, the all-reduce bus-bandwidth probe.  ``--dump-outputs DIR`` writes what the last timed step left a caller
+(loss, parameters, buffers) as ``DIR/<name>.npy``.
 
 One process per GPU (RCCL over xGMI for N > 1).  Model: ResNet-50, ImageNet layout (224x224x3 input,
 1000 classes), random init; data: synthetic device-resident tensors of that shape.  Compute dtype bf16
 (NHWC activations, fp32 accumulation, fp32 master weights / BN statistics / gradients), optimizer:
-fused SGD with momentum 0.9 + weight decay, full step timed (forward, backward, bucketed all-reduce,
-optimizer).  Per-GPU batch is fixed as N grows (weak scaling).  Rank 0 prints one JSON line with the
+fused SGD with momentum 0.9 + weight decay, lr 0.01 (``--lr``), the last BatchNorm gain of every bottleneck
+block initialised to 0.1 (``--residual-gain``; both recorded in the result's ``config``), full step timed
+(forward, backward, bucketed all-reduce, optimizer).  Per-GPU batch is fixed as N grows (weak scaling).  Rank 0 prints one JSON line with the
 WHOLE-JOB samples/sec (max step time over ranks).  Every N runs the DDP code path: at N = 1 the wrapper's
 bucket hooks all-reduce every bucket over a one-rank RCCL process group (BASELINE config 2, "DDP
-world_size=1"), and the plain single-GPU step is measured in a second process and reported beside it
-(``plain_step_1gpu``).
+world_size=1"), and with ``--full`` the plain single-GPU step is measured in a second process and reported
+beside it (``plain_step_1gpu``).
+
+The damped residual gains and the small learning rate are there for ``--dump-outputs``: at the model's own init
+(gain 1.0) with lr 0.1, the earlier defaults, the bf16 net is chaotic (two forwards over one set of weights differ
+by 5% in the logits) and no two runs compute the same thing; ``--residual-gain 1.0 --lr 0.1`` restores that setting, e.g. to compare ``final_loss`` with earlier records or tools/stock_baseline.py.  Neither value changes which
+kernels run or their time (12,220-12,250 img/s before, 12,260-12,290 after, same machine).
 
 ``--model gpt2_small`` benchmarks BASELINE.json config 4 instead: GPT-2 small (124M, T=1024, vocab
 50304), per-GPU batch 8 sequences, fused AdamW, metric tokens/sec (whole node).
@@ -140,6 +153,41 @@ def comm_diagnostics(net, step, n):
     return out
 
 
+DUMP_MAX_ELEMS = 4 * 2 ** 20      # per array: 16 MB of float32, the three arrays stay well under 64 MB in all
+
+
+def dump_outputs(out_dir, model, loss):
+    """``--dump-outputs``: what the training step hands its caller after the last timed step -- the loss it
+    returned and the model it updated (parameters, floating-point buffers) -- as float32 ``<name>.npy``.
+    Parameters and buffers are each flattened in registration order; an array longer than DUMP_MAX_ELEMS is
+    written as the elements at a fixed, seeded, sorted sample of positions, the same positions in every run.
+
+    The seeds fix the initial weights and the two batches, so the inputs of two runs are identical.  The kernels'
+    fp32 atomics (BatchNorm statistics, split-K reductions) change the summation order from run to run; with the
+    damped residual gains and lr 0.01 that stays at rounding level: pairs of runs of one build on one MI355X
+    differed (relative L2) by 4e-5 / 5e-4 / 1.2e-3 in loss / parameters / buffers after 40 steps and by 1.3e-4 /
+    8.5e-4 / 2.3e-3 after 60 (one pair each), below bf16's
+    2^-8.  (At --residual-gain 1.0 --lr 0.1 the net is chaotic: 0.20 / 0.30 / 0.33 after 25 steps.)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def flat(ts):
+        ts = [t.detach().to(torch.float32).reshape(-1) for t in ts]
+        return torch.cat(ts) if ts else torch.zeros(0)
+
+    arrays = {
+        "loss": loss.detach().to(torch.float32).reshape(1),
+        "params": flat([p for _, p in model.named_parameters()]),
+        "buffers": flat([b for _, b in model.named_buffers() if b.is_floating_point()]),
+    }
+    for name, t in arrays.items():
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(20240229).choice(n, DUMP_MAX_ELEMS, replace=False, shuffle=False))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -156,8 +204,13 @@ def main():
                          "32 / 64 / 128 MB equal there; at N > 1 the ddp.py cost model's 32 MB keeps every bucket but "
                          "the last under the backward)")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="at --gpus 1 (ResNet-50 headline), skip the child runs of BASELINE configs 4 and 5")
-    ap.add_argument("--lr", type=float, default=0.1)
+                    help="with --full at --gpus 1 (ResNet-50 headline), skip the child runs of BASELINE configs 4 and 5")
+    ap.add_argument("--lr", type=float, default=0.01,
+                    help="SGD learning rate (ResNets).  0.01 with the damped residual gains keeps the step-to-step "
+                         "growth of the kernels' fp32-atomic ordering noise below bf16 rounding over a run")
+    ap.add_argument("--residual-gain", type=float, default=0.1,
+                    help="initial gain of the last BatchNorm of every ResNet bottleneck block (1.0: the model's own "
+                         "init, under which the bf16 step is chaotic and --dump-outputs does not repeat)")
     ap.add_argument("--fp8", action="store_true",
                     help="BASELINE config 5: ResNet 3x3 convs / GPT-2 forward linears on the fp8 MFMA kernels")
     ap.add_argument("--graph", default="auto", choices=["off", "on", "auto", "collectives"],
@@ -168,15 +221,25 @@ def main():
     ap.add_argument("--plain", action="store_true",
                     help="one GPU without the DDP wrapper and process group (the second run of a --gpus 1 bench)")
     ap.add_argument("--no-ddp-rehearsal", "--no-plain-run", dest="no_plain_run", action="store_true",
-                    help="at --gpus 1, skip the second measurement (the plain step)")
+                    help="with --full at --gpus 1, skip the second measurement (the plain step)")
     ap.add_argument("--opt-overlap", action="store_true",
                     help="DDP path: apply the optimizer per bucket during the backward instead of after it")
     ap.add_argument("--diag-steps", type=int, default=5,
-                    help="DDP path: extra steps after the timed region with per-bucket communication timing")
+                    help="DDP path with --full: extra steps after the timed region with per-bucket communication "
+                         "timing")
     ap.add_argument("--hang-timeout", type=float, default=90.0,
                     help="N > 1: hang watchdog (s without a completed step; the process-group timeout is 1.25x): "
                          "on a hang every rank prints one diagnostic JSON line and exits 75")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the secondary measurements: the plain single-GPU step and "
+                         "BASELINE configs 4 / 5 in child processes, the per-bucket communication timing and, at "
+                         "N > 1, the all-reduce bus-bandwidth probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left a caller (loss, parameters, buffers) "
+                         "as DIR/<name>.npy in float32; arrays over the size cap as a fixed seeded sample")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.bucket_mb is None:
         n_world = int(os.environ.get("WORLD_SIZE", "1"))
         a.bucket_mb = 256.0 if a.model.lower().startswith("gpt2") and n_world == 1 else 32.0
@@ -221,6 +284,17 @@ def main():
     nc = 10 if small else 1000
     in_chw = (1, 28, 28) if a.model.lower() == "lenet" else (3, 32, 32) if small else (3, a.image_size, a.image_size)
     model = build_model(a.model, num_classes=nc).to(dev)
+    residual_damped = False
+    if a.residual_gain != 1.0:
+        # damped residual branches (the last BatchNorm gain of every bottleneck block): at its plain random init a
+        # bf16 ResNet-50 is chaotic -- two forwards over the same weights and batch differ by 5% in the logits and
+        # 100% in the gradients, grown from the fp32 atomic order of the BatchNorm statistics -- so no two runs
+        # would compute the same outputs.  The values do not change which kernels run or how long they take.
+        with torch.no_grad():
+            for mod in model.modules():
+                if hasattr(mod, "bn3"):           # bottleneck blocks only: other models keep their own init
+                    mod.bn3.weight.fill_(a.residual_gain)
+                    residual_damped = True
     if a.fp8:
         if lm:
             model.config.fp8 = True
@@ -336,6 +410,9 @@ def main():
         runtime.barrier()
         sync()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and env.rank == 0:
+        # before anything below runs further steps: the state the last timed step left
+        dump_outputs(a.dump_outputs, model, loss)
     host_probe = None
     if os.environ.get("PDNN_BENCH_HOST_PROBE") and dev.type == "cuda":
         # diagnostics after the timed region: host enqueue time of one step started on an idle GPU vs the step's
@@ -360,7 +437,7 @@ def main():
                 sync()
                 pstats.Stats(pr, stream=sys.stderr).sort_stats("tottime").print_stats(40)
     comm = None
-    if use_ddp and not use_graph and isinstance(net, DistributedDataParallel) and dev.type == "cuda":
+    if a.full and use_ddp and not use_graph and isinstance(net, DistributedDataParallel) and dev.type == "cuda":
         # after the timed region (it is not perturbed): a few more steps with device-event timing of every bucket
         # all-reduce, the exposed tail and the BN-buffer broadcast -- fp32 wire, then bf16 wire
         with ctx:
@@ -368,7 +445,10 @@ def main():
     if use_ddp and not on_gpu and isinstance(net, DistributedDataParallel):
         comm = {"bucket_mb": [round(v, 3) for v in net.bucket_sizes_mb()], "world": net.world, "fp32": None,
                 "bf16": None, "note": "per-bucket device timing needs a GPU (CPU rehearsal)"}
-    if world > 1 and isinstance(comm, dict):
+    if comm is None and use_ddp and not use_graph and isinstance(net, DistributedDataParallel):
+        comm = {"bucket_mb": [round(v, 3) for v in net.bucket_sizes_mb()], "world": net.world, "fp32": None,
+                "bf16": None, "note": "per-bucket device timing runs with --full"}
+    if a.full and world > 1 and isinstance(comm, dict):
         # bus bandwidth of the bucket-size collectives on this node (after the timed region)
         comm["allreduce_busbw"] = allreduce_probe(dev, world, iters=3 if not on_gpu else 10,
                                                   warmup=1 if not on_gpu else 3,
@@ -390,11 +470,11 @@ def main():
     # over a one-rank process group) is measured in a child process and reported alongside, so a scaling
     # efficiency can be read against either.
     plain = None
-    if world == 1 and use_ddp and not a.no_plain_run and env.rank == 0:
+    if a.full and world == 1 and use_ddp and not a.no_plain_run and env.rank == 0:
         plain = _plain_run(a)
     extra = None
-    if (world == 1 and on_gpu and not a.plain and not a.no_extra_configs and a.model == "resnet50" and not a.fp8
-            and env.rank == 0):
+    if (a.full and world == 1 and on_gpu and not a.plain and not a.no_extra_configs and a.model == "resnet50"
+            and not a.fp8 and env.rank == 0):
         extra = {name: _child_run(a, args) for name, args in EXTRA_CONFIGS}
     if lm and env.rank == 0:
         tok = value * S
@@ -441,7 +521,7 @@ def main():
                                       if a.model == "resnet50" and B == 256 and not a.fp8 else None),
             "dtype": "fp8 3x3 convs (e4m3 fwd / e5m2 dgrad) + bf16" if a.fp8 else "bf16" if on_gpu else "fp32 (CPU rehearsal)",
             "data": f"synthetic (device-resident random {in_chw[1]}x{in_chw[2]}x{in_chw[0]} images, random labels), "
-                    "random-init weights",
+                    "random-init weights" + (f" (bottleneck bn3 gain {a.residual_gain:g})" if residual_damped else ""),
             "final_loss": round(float(loss.detach()), 4),
             "native_loaded": native_loaded(),
             "n1_point": "plain single-GPU step" if not use_ddp else
@@ -454,7 +534,8 @@ def main():
                                  f"{a.model} (ImageNet layout, {S}x{S}, {nc} classes)"), "global_batch": B * world,
                        "per_gpu_batch": B, "seq_len": None, "image_size": S, "parallelism": f"dp{world}",
                        "optimizer": "fused SGD momentum=0.9 wd=5e-5", "bucket_mb": a.bucket_mb, "hipgraph": use_graph,
-                       "opt_overlap": opt_overlap},
+                       "opt_overlap": opt_overlap, "lr": a.lr,
+                       "residual_gain": a.residual_gain if residual_damped else None},
         })
     runtime.destroy()
 

@@ -28,6 +28,8 @@ model with world size > 1 would capture its RCCL all-reduces too; that is opt-in
 """
 from __future__ import annotations
 
+import time
+
 import torch
 
 
@@ -85,6 +87,14 @@ class GraphedStep:
         self.static_x = x.detach().clone()
         self.static_y = y.detach().clone()
         torch.cuda.synchronize()
+        if self.allow_collectives:
+            # the process group's watchdog thread polls the end events of the eager warm-up collectives until it has
+            # seen them complete.  Those events were recorded on RCCL's internal stream, which the capture below pulls
+            # in: hipEventQuery then fails with hipErrorCapturedEvent and the watchdog aborts the process.  Everything
+            # is complete after the synchronize, but torch exposes no call that waits for the watchdog to retire its
+            # list, so this waits five of its sweeps (ProcessGroupNCCL sleeps 100 ms between sweeps): it relies on
+            # that period, once per capture
+            time.sleep(0.5)
         self.opt.graph_mode(True)
         self.graph = torch.cuda.CUDAGraph()
         # thread_local: a data-loader thread doing its own H2D copies must not invalidate the capture

@@ -32,7 +32,7 @@ def _json_lines(out):
 
 
 def test_bench_world2_prints_one_line_with_comm_block():
-    r = _torchrun(2, ["--model", "lenet", "--steps", "3", "--warmup", "1"], {}, 300)
+    r = _torchrun(2, ["--model", "lenet", "--steps", "3", "--warmup", "1", "--full"], {}, 300)
     assert r.returncode == 0, r.stderr[-3000:]
     recs = _json_lines(r.stdout)
     assert len(recs) == 1, r.stdout                      # rank 0 only
@@ -46,6 +46,62 @@ def test_bench_world2_prints_one_line_with_comm_block():
     bw = rec["comm"]["allreduce_busbw"]
     assert {b["dtype"] for b in bw} == {"float32", "bfloat16"} and all(b["busbw_GBps"] > 0 for b in bw)
     assert rec["extra_configs"] is None          # the config-4/5 child runs belong to the 1-GPU command only
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the run only times its steps (no bus-bandwidth probe, no child runs); --dump-outputs writes the
+    last step's loss and the model it left as float32 arrays, identical between two runs of this deterministic CPU
+    path (same seeds, same inputs)."""
+    import numpy as np
+    args = ["--model", "lenet", "--steps", "2", "--warmup", "1", "--dump-outputs"]
+    recs = []
+    cpu_only = {"HIP_VISIBLE_DEVICES": "", "CUDA_VISIBLE_DEVICES": ""}      # bitwise equality holds for the CPU path
+    for d in ("a", "b"):
+        r = _torchrun(2, args + [str(tmp_path / d)], cpu_only, 300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        recs.append(_json_lines(r.stdout))
+    assert len(recs[0]) == 1, recs[0]
+    rec = recs[0][0]
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+    assert rec["dtype"] == "fp32 (CPU rehearsal)"
+    assert "allreduce_busbw" not in rec["comm"] and rec["plain_step_1gpu"] is None and rec["extra_configs"] is None
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["buffers.npy", "loss.npy", "params.npy"] == sorted(os.listdir(tmp_path / "b"))
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and np.isfinite(x).all()
+        assert np.array_equal(x, y), n
+        total += x.nbytes
+    assert 0 < total <= 64 * 2 ** 20
+    assert abs(float(np.load(tmp_path / "a" / "loss.npy")[0]) - rec["final_loss"]) < 1e-3
+    assert np.load(tmp_path / "a" / "params.npy").size == 431080       # every LeNet parameter, unsampled
+
+
+def test_bench_world1_full_gates_the_plain_step_child_run():
+    """World 1 through the DDP path (the --gpus 1 command, here on the CPU over gloo): the second measurement, the
+    plain step in a child process, runs only with --full; the result line records lr and the residual gain."""
+    env = dict(os.environ, PDNN_BENCH_BACKEND="gloo", OMP_NUM_THREADS="1", HIP_VISIBLE_DEVICES="",
+               CUDA_VISIBLE_DEVICES="")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "PDNN_FORCE_PG", "PDNN_DDP_FORCE_COMM"):
+        env.pop(k, None)
+    recs = {}
+    for full in (False, True):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", "lenet", "--steps", "2",
+               "--warmup", "1"] + (["--full"] if full else [])
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd="/tmp")
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1, r.stdout
+        recs[full] = lines[0]
+    for rec in recs.values():
+        assert rec["n_gpus"] == 1 and rec["steps"] == 2 and rec["n1_point"].startswith("DDP path")
+        assert rec["comm"]["world"] == 1 and "allreduce_busbw" not in rec["comm"]
+        assert rec["config"]["lr"] == 0.01 and rec["config"]["residual_gain"] is None     # LeNet: no bottlenecks
+        assert rec["extra_configs"] is None                                              # GPU runs only
+    assert recs[False]["plain_step_1gpu"] is None
+    plain = recs[True]["plain_step_1gpu"]
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0, plain
 
 
 def test_bench_world2_gpt2_split_tied_embedding():

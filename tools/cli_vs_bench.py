@@ -5,7 +5,8 @@ python tools/cli_vs_bench.py METRICS.jsonl BENCH.json [--batch 256]
 METRICS.jsonl is ``cli.py --metrics``: every log-interval record carries ``wall_s``, taken after that step
 completed on the device.  The CLI throughput is (steps between the first and last logged record) x batch /
 elapsed wall time -- the same whole-step, host-included measure as bench.py's timed loop.  Prints one JSON
-line with both numbers and their ratio."""
+line with both numbers and their ratio.  BENCH.json is the result line of ``bench.py --full`` (the plain
+step is measured only there)."""
 import argparse
 import json
 
