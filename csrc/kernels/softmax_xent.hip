@@ -134,12 +134,15 @@ __global__ void __launch_bounds__(NT) xent_bwd_kernel(const T* __restrict__ logi
 // the row is held in registers (MAXC 16-byte chunks per lane, V <= 8 * NT * MAXC), so it is read from HBM once
 // and written once -- the separate backward pass (a second full read of the logits) disappears.  The caller
 // applies grad_out / count to the products of the gradient (the LM head's 8192 x 768 operands), not to it.
+// logits may alias dlogits (no __restrict__ on either), so nothing is read from the row in global memory after the
+// first store: the target logit for the loss goes from its owner's registers through a shared slot.
 template <int MAXC>
-__global__ void __launch_bounds__(NT) xent_fwd_grad_kernel(const bf16_t* __restrict__ logits, long ld, int V,
+__global__ void __launch_bounds__(NT) xent_fwd_grad_kernel(const bf16_t* logits, long ld, int V,
                                                            const int64_t* __restrict__ labels, int ignore,
                                                            float* __restrict__ loss, float* __restrict__ lse,
                                                            bf16_t* dlogits, long ldd) {
     __shared__ float red[NT / 64];
+    __shared__ float xy;                    // logits[row][y], written by the lane that holds chunk y / 8
     const long row = blockIdx.x;
     const u16x8_t* x8 = reinterpret_cast<const u16x8_t*>(logits + row * ld);
     u16x8_t* d8 = reinterpret_cast<u16x8_t*>(dlogits + row * ldd);
@@ -180,12 +183,24 @@ __global__ void __launch_bounds__(NT) xent_fwd_grad_kernel(const bf16_t* __restr
             for (int j = 0; j < 8; ++j) sum += __expf(v[j] - M);
         }
     }
-    const float l = M + __logf(block_sum<NT>(sum, red));
     const int64_t y = labels[row];
     const bool ign = (y == ignore || y < 0 || y >= V);
+    const int cy = ign ? -1 : (int)y >> 3;      // the 16-byte chunk of the label; -1 matches no lane
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c) {            // compile-time c: r[] stays in registers
+        if ((int)threadIdx.x + c * NT == cy) {
+            float v[8];
+            unpack8(r[c], v);
+            float t = v[0];
+#pragma unroll
+            for (int j = 1; j < 8; ++j) t = ((int)y & 7) == j ? v[j] : t;
+            xy = t;
+        }
+    }
+    const float l = M + __logf(block_sum<NT>(sum, red));      // its barriers order the write of xy before the read
     if (threadIdx.x == 0) {
         lse[row] = l;
-        loss[row] = ign ? 0.f : l - bf2f(logits[row * ld + y]);
+        loss[row] = ign ? 0.f : l - xy;
     }
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {

@@ -855,11 +855,20 @@ def avgpool_bwd(dy, x_shape):
 
 
 # ----------------------------------------------------------------------------------- loss
+def _xent_rows(labels, R, lse=None):
+    """The per-row operands the kernels index by row without a bound of their own."""
+    _chk(labels.dtype == torch.int64 and labels.dim() == 1 and labels.numel() == R and labels.is_contiguous()
+         and labels.is_cuda, "xent: labels must be contiguous int64 [rows] on the device")
+    _chk(lse is None or (lse.dtype == F32 and lse.dim() == 1 and lse.numel() == R and lse.is_contiguous()
+                         and lse.is_cuda), "xent: lse must be contiguous fp32 [rows] on the device")
+
+
 def xent_fwd(logits, labels, ignore_index=-100):
     R, V = logits.shape
     _chk(logits.stride(1) == 1, "xent: row-major logits")
     dt = 1 if logits.dtype == BF16 else 0
     _chk(logits.dtype in (BF16, F32), "xent: bf16/fp32 logits")
+    _xent_rows(labels, R)
     loss = torch.empty(R, device=logits.device, dtype=F32)
     lse = torch.empty(R, device=logits.device, dtype=F32)
     acc = torch.empty(2, device=logits.device, dtype=F32)          # [loss sum, valid-label count], set by the call
@@ -885,6 +894,7 @@ def xent_fwd_grad(logits, labels, ignore_index=-100, out=None):
     d = logits if out is None else out
     _chk(d.shape == logits.shape and d.dtype == BF16 and d.stride(1) == 1 and d.stride(0) % 8 == 0
          and d.data_ptr() % 16 == 0, "xent_fwd_grad: bf16 row-major output")
+    _xent_rows(labels, R)
     loss = torch.empty(R, device=logits.device, dtype=F32)
     lse = torch.empty(R, device=logits.device, dtype=F32)
     acc = torch.empty(2, device=logits.device, dtype=F32)
@@ -897,9 +907,13 @@ def xent_bwd(logits, labels, lse, gscale_dev, denom, ignore_index=-100, count=No
     """d logits = softmax - onehot, times gscale_dev[0] / denom, or gscale_dev[0] / max(count[0], 1) with
     ``count`` (fp32 device scalar: xent_fwd's count of non-ignored rows, the mean reduction)."""
     R, V = logits.shape
+    _chk(logits.stride(1) == 1 and logits.dtype in (BF16, F32), "xent_bwd: row-major bf16/fp32 logits")
+    _xent_rows(labels, R, lse)
     d = torch.empty_like(logits)
     dt = 1 if logits.dtype == BF16 else 0
     _chk(gscale_dev.dtype == F32 and gscale_dev.is_cuda, "xent_bwd: fp32 device gscale")
+    _chk(count is None or (count.dtype == F32 and count.is_cuda and count.numel() >= 1),
+         "xent_bwd: fp32 device count")
     call("pdnn_xent_bwd", ptr(logits), logits.stride(0), R, V, ptr(labels), int(ignore_index), ptr(lse),
          ptr(gscale_dev), float(denom), ptr(count), ptr(d), d.stride(0), dt, stream())
     return d

@@ -112,6 +112,50 @@ def test_ddp_rccl_single_rank_rehearsal():
     assert min(moved) > 0, moved
 
 
+def _rccl_split_tied_job(rank, world):
+    """One gpt2_tiny step with the tied wte gradient split (dense LM-head part in bucket 0, embedding rows added at
+    the end of the backward by the embedding kernel with the position table absent) and one with it unsplit, from the
+    same seed and batch, over RCCL at world 1."""
+    import torch.distributed as dist
+    from pytorch_distributed_nn_amd.models import build_model
+    from pytorch_distributed_nn_amd.parallel.ddp import DistributedDataParallel
+    assert dist.get_backend() == "nccl" and dist.get_world_size() == 1
+    dev = torch.device("cuda")
+    data = torch.randint(0, 512, (2, 129), generator=torch.Generator().manual_seed(4))
+    data[:, 40:70] = 11                                   # repeated token ids: many rows into one wte row
+    data[1, :20] = data[0, :20]
+    data = data.to(dev)
+    out = {}
+    for split in (True, False):
+        torch.manual_seed(0)
+        m = build_model("gpt2_tiny").to(dev)
+        net = DistributedDataParallel(m, bucket_cap_mb=0.25, split_tied=split)
+        assert net._comm and net.nccl
+        net.zero_grad()
+        net(data[:, :-1].contiguous(), data[:, 1:].contiguous()).backward()
+        torch.cuda.synchronize()
+        wte = m.transformer.wte.weight
+        out[split] = {"flat": net.flat.grad.clone(), "wte": wte.grad.clone(),
+                      "wpe": m.transformer.wpe.weight.grad.clone(), "split": net._tail is not None,
+                      "bucket": net._pbucket[id(wte)], "nb": len(net.buckets), "order": list(net.last_launch_order)}
+    return out
+
+
+def test_ddp_rccl_split_tied_embedding_matches_unsplit():
+    """The embedding half of the tied wte gradient in its split form on the GPU kernels: flat gradient, wte.grad and
+    wpe.grad equal the unsplit path's to 1e-4 relative L2 (the bound for the same gradient accumulated in another
+    atomic order, as in test_gpt2_side_stream_weight_gradients), and the wte bucket is launched first."""
+    res = run_world(_rccl_split_tied_job, 1, (), timeout=300, device=None, backend="nccl",
+                    env={"PDNN_FORCE_PG": "1", "PDNN_DDP_FORCE_COMM": "1"})[0]
+    s, u = res[True], res[False]
+    assert s["split"] and not u["split"]
+    assert s["nb"] >= 2 and s["bucket"] == 0 and s["order"][0] == 0
+    for k in ("flat", "wte", "wpe"):
+        assert torch.isfinite(s[k]).all() and u[k].norm().item() > 0, k
+        rel = ((s[k] - u[k]).norm() / u[k].norm()).item()
+        assert rel <= 1e-4, (k, rel)
+
+
 def _rccl_kofn_job(rank, world):
     """The k-of-n collective control plane on RCCL at world 1 (PDNN_FORCE_PG): store reports, watcher
     thread, host throttle against CUDA events, zero-fill path and the per-bucket count all-reduce."""

@@ -132,6 +132,50 @@ def test_embedding(K):
     assert rel(dwte, rte) < 1e-4 and rel(dwpe, rpe) < 1e-4
 
 
+@pytest.mark.parametrize("D", [8, 264])
+def test_embedding_bwd_split_and_scaled(K, D):
+    """The split form of the tied-embedding gradient: embedding_bwd with only the token table, only the position
+    table, and with ``scale`` on the token rows beside an unscaled position table.  Each entry against a float64
+    index_add_ at 1e-5 relative.  The gradient rows are positive, so an entry is an fp32 sum of n same-sign bf16
+    values on top of the 1 it held: every atomic add rounds by at most 2^-24 of a partial sum that is below the
+    final value, n * 2^-24 in all, which stays under 1e-5 up to n = 167 contributions.  The most-hit row here gets
+    about 105 (100 repeats of one id among R = 300 rows, R no multiple of the 256-lane block or of T), asserted
+    below."""
+    V, Tm, R, T = 1000, 64, 300, 48
+    gen = torch.Generator(device="cuda").manual_seed(21 + D)
+    idx = torch.randint(0, V, (R,), device="cuda", generator=gen)
+    idx[100:200] = 7                                  # repeated ids accumulate into one row
+    idx[R - 1] = V - 1
+    pos = torch.arange(R, device="cuda") % T
+    assert int(torch.bincount(idx).max()) <= 167 and int(torch.bincount(pos).max()) <= 167
+    g = (torch.rand(R, D, device="cuda", generator=gen) + 0.5).to(BF)
+    g64 = g.double()
+
+    def ones(n):
+        return torch.ones(n, D, device="cuda")
+
+    def close(a, ref):
+        return bool(((a.double() - ref).abs() <= 1e-5 * ref.abs()).all())
+
+    rte = torch.ones(V, D, device="cuda", dtype=torch.float64).index_add_(0, idx, g64)
+    rte_half = torch.ones(V, D, device="cuda", dtype=torch.float64).index_add_(0, idx, 0.5 * g64)
+    rpe = torch.ones(Tm, D, device="cuda", dtype=torch.float64).index_add_(0, pos, g64)
+    dwte = ones(V)
+    K.embedding_bwd(idx, g, dwte, None, T)
+    assert close(dwte, rte)
+    dwpe = ones(Tm)
+    K.embedding_bwd(idx, g, None, dwpe, T)
+    assert close(dwpe, rpe)
+    assert bool((dwpe[T:] == 1.0).all())               # positions past T are never touched
+    dwte, dwpe = ones(V), ones(Tm)
+    K.embedding_bwd(idx, g, dwte, dwpe, T, scale=0.5)
+    assert close(dwte, rte_half)
+    assert close(dwpe, rpe)                            # scale applies to the token rows only
+    untouched = torch.ones(V, dtype=torch.bool, device="cuda")
+    untouched[idx] = False
+    assert bool((dwte[untouched] == 1.0).all())
+
+
 def _tiny(seed=0, **kw):
     from pytorch_distributed_nn_amd.models.gpt2 import build_gpt2
     torch.manual_seed(seed)
