@@ -395,7 +395,13 @@ inline unsigned bn_stream_grid(long work) {
     return (unsigned)(g < 1 ? 1 : g);
 }
 
-inline unsigned reduce_grid(long L, int C) {
+// What every launcher below accepts: 8 channels per thread, at most NT channel groups (RPI = NT / (C/8) >= 1),
+// at least one row.  Checked on the host before anything is launched (hipErrorInvalidValue otherwise).
+inline bool bn_c_ok(int C) { return C >= 8 && C % 8 == 0 && C <= 8 * NT; }
+inline bool bn_shape_ok(long L, int C) { return L >= 1 && bn_c_ok(C); }
+#define PDNN_BN_REQUIRE(cond) do { if (!(cond)) return (int)hipErrorInvalidValue; } while (0)
+
+inline unsigned reduce_grid(long L, int C) {      // callers check bn_c_ok(C) first
     const int rpi = NT / (C / 8);
     long g = (L + rpi * BN_RMIN - 1) / (rpi * BN_RMIN);   // >= BN_RMIN rows per thread-row
     if (g > 512) g = 512;
@@ -404,13 +410,14 @@ inline unsigned reduce_grid(long L, int C) {
 }
 }  // namespace
 
-PDNN_API int pdnn_bn_reduce_rows(long L, int C) { return (int)reduce_grid(L, C); }
+PDNN_API int pdnn_bn_reduce_rows(long L, int C) { return bn_c_ok(C) ? (int)reduce_grid(L, C) : 0; }
 
 // slab = STAT_BINS bins [64][2][C] (common.h), left zeroed.  rows: kept in the signature (= STAT_BINS)
 PDNN_API int pdnn_bn_finalize(float* slab, int rows, int C, double L, float eps, float momentum,
                               const float* gamma, const float* beta, float* run_mean, float* run_var,
                               float* mean_out, float* invstd_out, float* scale_out, float* shift_out, hipStream_t st) {
     if (rows != STAT_BINS) return (int)hipErrorInvalidValue;
+    PDNN_BN_REQUIRE(bn_c_ok(C) && L >= 1 && slab && scale_out && shift_out && (!run_mean == !run_var));
     const FinFwd epi{L, eps, momentum, gamma, beta, run_mean, run_var, mean_out, invstd_out, scale_out, shift_out};
     hipLaunchKernelGGL(bn_bins_final_kernel<FinFwd>, dim3((C + 63) / 64), dim3(NT), 0, st, slab, C, epi);
     PDNN_LAUNCH_RET;
@@ -418,12 +425,14 @@ PDNN_API int pdnn_bn_finalize(float* slab, int rows, int C, double L, float eps,
 
 PDNN_API int pdnn_bn_eval_coeff(int C, float eps, const float* gamma, const float* beta, const float* rm,
                                 const float* rv, float* scale, float* shift, hipStream_t st) {
+    PDNN_BN_REQUIRE(C >= 1 && rm && rv && scale && shift);
     hipLaunchKernelGGL(bn_eval_coeff_kernel, dim3((C + 255) / 256), dim3(256), 0, st, C, eps, gamma, beta,
                        rm, rv, scale, shift);
     PDNN_LAUNCH_RET;
 }
 
 PDNN_API int pdnn_bn_stats(const bf16_t* x, long L, int C, float* slab, hipStream_t st) {
+    PDNN_BN_REQUIRE(bn_shape_ok(L, C) && x && slab);
     hipLaunchKernelGGL(bn_stats_kernel, dim3(reduce_grid(L, C)), dim3(NT), 0, st, x, L, C, slab);
     PDNN_LAUNCH_RET;
 }
@@ -432,6 +441,9 @@ PDNN_API int pdnn_bn_stats(const bf16_t* x, long L, int C, float* slab, hipStrea
 PDNN_API int pdnn_bn_apply(const bf16_t* x, long L, int C, const float* scale, const float* shift,
                            const bf16_t* res, const float* rscale, const float* rshift, int relu, bf16_t* y,
                            uint8_t* mbits, hipStream_t st) {
+    // the dispatch below has no (mask bits, no ReLU) kernel; a scaled residual needs both coefficient vectors
+    PDNN_BN_REQUIRE(bn_shape_ok(L, C) && x && scale && shift && y && (!mbits || relu));
+    PDNN_BN_REQUIRE(res ? (!rscale == !rshift) : (!rscale && !rshift));
     const dim3 grid(bn_stream_grid(L * (C / 8)));
 #define PDNN_BA(RES, RSC, RELU, MASK)                                                                  \
     hipLaunchKernelGGL((bn_apply_kernel<RES, RSC, RELU, MASK>), grid, dim3(NT), 0, st, x, L, C, scale, shift, res, \
@@ -451,6 +463,10 @@ PDNN_API int pdnn_bn_bwd_reduce(const bf16_t* g, const bf16_t* x, long L, int C,
                                 const float* invstd, int mode, const bf16_t* msrc, const float* mscale,
                                 const float* mshift, float* slab, const bf16_t* x2, const float* mean2,
                                 const float* invstd2, float* slab2, hipStream_t st) {
+    PDNN_BN_REQUIRE(bn_shape_ok(L, C) && g && x && mean && invstd && slab && mode >= 0 && mode <= 3);
+    PDNN_BN_REQUIRE((mode != 1 && mode != 3) || msrc);
+    PDNN_BN_REQUIRE(mode != 2 || (mscale && mshift));
+    PDNN_BN_REQUIRE(x2 ? (mean2 && invstd2 && slab2) : !slab2);
 #define PDNN_BWR(MODE, X2)                                                                                  \
     hipLaunchKernelGGL((bn_bwd_reduce_kernel<MODE, X2>), dim3(reduce_grid(L, C)), dim3(NT), 0, st, g, x, L, C, \
                        mean, invstd, msrc, mscale, mshift, slab, x2, mean2, invstd2, slab2)
@@ -470,6 +486,7 @@ PDNN_API int pdnn_bn_bwd_reduce(const bf16_t* g, const bf16_t* x, long L, int C,
 PDNN_API int pdnn_bn_bwd_finalize(float* slab, int rows, int C, float* dgamma, float* dbeta, int accumulate,
                                   float* gacc, float* bacc, hipStream_t st) {
     if (rows != STAT_BINS) return (int)hipErrorInvalidValue;
+    PDNN_BN_REQUIRE(bn_c_ok(C) && slab && dgamma && dbeta && (!gacc == !bacc));
     const FinBwd epi{dgamma, dbeta, accumulate, gacc, bacc};
     hipLaunchKernelGGL(bn_bins_final_kernel<FinBwd>, dim3((C + 63) / 64), dim3(NT), 0, st, slab, C, epi);
     PDNN_LAUNCH_RET;
@@ -481,6 +498,14 @@ PDNN_API int pdnn_bn_bwd_apply(const bf16_t* g, const bf16_t* x, long L, int C, 
                                const float* mshift, bf16_t* dx, const bf16_t* x2, const float* mean2,
                                const float* invstd2, const float* gamma2, const float* dgamma2,
                                const float* dbeta2, bf16_t* dx2, bf16_t* gm_out, hipStream_t st) {
+    PDNN_BN_REQUIRE(bn_shape_ok(L, C) && g && x && mean && invstd && dgamma && dbeta && mode >= 0 && mode <= 3);
+    PDNN_BN_REQUIRE((mode != 1 && mode != 3) || msrc);
+    PDNN_BN_REQUIRE(mode != 2 || (mscale && mshift));
+    PDNN_BN_REQUIRE(x2 ? (mean2 && invstd2 && dgamma2 && dbeta2 && dx2) : !dx2);
+    // variants the table below has no kernel for: a second BN with mask mode 2, gm_out without a mask, and a call
+    // without dx that is not (modes 1 / 3, no second BN, gm_out)
+    PDNN_BN_REQUIRE(!(x2 && mode == 2) && !(gm_out && mode == 0));
+    PDNN_BN_REQUIRE(dx || (gm_out && !x2 && (mode == 1 || mode == 3)));
     const dim3 grid(bn_stream_grid(L * (C / 8)));
 #define PDNN_BWA(MODE, X2, DX, GMO)                                                                              \
     hipLaunchKernelGGL((bn_bwd_apply_kernel<MODE, X2, DX, GMO>), grid, dim3(NT), 0, st, g, x, L, C, mean, invstd, \

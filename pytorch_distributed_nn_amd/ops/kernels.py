@@ -602,13 +602,61 @@ def _release_bins(slab):
     _BINS.setdefault(_bins_key(slab.device, slab.shape[1]), []).append(slab)
 
 
+# Host-side contract of the BatchNorm entry points (csrc/kernels/batchnorm.hip): each thread owns 8 channels and a
+# block has 256 of them, so C % 8 == 0 and C <= 2048; operands are contiguous [L][C] bf16 with per-channel fp32
+# vectors of length C.  Integer / dtype / is_contiguous comparisons only: these run ~100 times per step on the host's
+# critical path (no .item(), no synchronisation, no allocation).
+
+
+def _bn_c(C, name):
+    _chk(C % 8 == 0 and 8 <= C <= 2048, f"{name}: C % 8 == 0 and 8 <= C <= 2048 required, got C={C}")
+
+
+def _bn_act(t, L, C, name):
+    _chk(t is not None and t.dtype == BF16 and t.is_cuda and t.dim() == 2 and t.shape[0] == L and t.shape[1] == C
+         and t.is_contiguous(), f"{name}: expected a contiguous CUDA bf16 [{L}][{C}] tensor")
+
+
+def _bn_vec(t, C, name, optional=False):
+    if t is None:
+        _chk(optional, f"{name}: required")
+        return
+    _chk(t.dtype == F32 and t.is_cuda and t.numel() == C and t.is_contiguous(),
+         f"{name}: expected a contiguous CUDA fp32 vector of {C}")
+
+
+def _bn_slab(slab, rows, name):
+    _chk(slab.dtype == F32 and slab.is_cuda and slab.dim() == 2 and rows == STAT_BINS
+         and slab.shape[0] == 2 * STAT_BINS and slab.is_contiguous(), f"{name}: a stat_bins() slab")
+    _bn_c(slab.shape[1], name)
+
+
+def _bn_mask(mode, msrc, mscale, mshift, L, C, name):
+    _chk(mode in (0, 1, 2, 3), f"{name}: mask mode 0..3, got {mode!r}")
+    if mode == 1:
+        _bn_act(msrc, L, C, f"{name}: msrc (mask mode 1)")
+    elif mode == 3:
+        _chk(msrc is not None and msrc.dtype == torch.uint8 and msrc.is_cuda and msrc.dim() == 2 and msrc.shape[0] == L
+             and msrc.shape[1] == C // 8 and msrc.is_contiguous(),
+             f"{name}: msrc (mask mode 3) must be bn_apply's uint8 [{L}][{C // 8}] sign bits")
+    elif mode == 2:
+        _bn_vec(mscale, C, f"{name}: mscale (mask mode 2)")
+        _bn_vec(mshift, C, f"{name}: mshift (mask mode 2)")
+
+
 def bn_finalize(slab, rows, L, eps, momentum, gamma, beta, run_mean, run_var):
+    _bn_slab(slab, rows, "bn_finalize")
     C = slab.shape[1]
+    _chk(L >= 1, f"bn_finalize: L={L}")
+    _bn_vec(gamma, C, "bn_finalize: gamma", True)
+    _bn_vec(beta, C, "bn_finalize: beta", True)
+    _chk((run_mean is None) == (run_var is None), "bn_finalize: run_mean and run_var go together")
+    _bn_vec(run_mean, C, "bn_finalize: run_mean", True)
+    _bn_vec(run_var, C, "bn_finalize: run_var", True)
     mean = torch.empty(C, device=slab.device, dtype=F32)
     invstd = torch.empty_like(mean)
     scale = torch.empty_like(mean)
     shift = torch.empty_like(mean)
-    _chk(rows == STAT_BINS and slab.shape[0] == 2 * STAT_BINS, "bn_finalize: a stat_bins() slab")
     call("pdnn_bn_finalize", ptr(slab), rows, C, float(L), float(eps), float(momentum), ptr(gamma), ptr(beta),
          ptr(run_mean), ptr(run_var), ptr(mean), ptr(invstd), ptr(scale), ptr(shift), stream())
     _release_bins(slab)
@@ -616,7 +664,12 @@ def bn_finalize(slab, rows, L, eps, momentum, gamma, beta, run_mean, run_var):
 
 
 def bn_eval_coeff(eps, gamma, beta, rm, rv):
+    _chk(rm is not None and rm.numel() >= 1, "bn_eval_coeff: running statistics required")
     C = rm.numel()
+    _bn_vec(rm, C, "bn_eval_coeff: running mean")
+    _bn_vec(rv, C, "bn_eval_coeff: running var")
+    _bn_vec(gamma, C, "bn_eval_coeff: gamma", True)
+    _bn_vec(beta, C, "bn_eval_coeff: beta", True)
     scale = torch.empty(C, device=rm.device, dtype=F32)
     shift = torch.empty_like(scale)
     call("pdnn_bn_eval_coeff", C, float(eps), ptr(gamma), ptr(beta), ptr(rm), ptr(rv), ptr(scale), ptr(shift),
@@ -625,8 +678,10 @@ def bn_eval_coeff(eps, gamma, beta, rm, rv):
 
 
 def bn_stats(x2d):
+    _chk(x2d.dim() == 2, "bn_stats: x [L][C]")
     L, C = x2d.shape
-    _chk(C % 8 == 0 and C <= 2048, f"bn_stats: C={C}")
+    _chk(C % 8 == 0 and 8 <= C <= 2048 and L >= 1, f"bn_stats: L={L} C={C}")
+    _bn_act(x2d, L, C, "bn_stats: x")
     slab = stat_bins(C, x2d.device)
     call("pdnn_bn_stats", ptr(x2d), L, C, ptr(slab), stream())
     return slab, STAT_BINS
@@ -636,9 +691,24 @@ def bn_apply(x2d, scale, shift, res=None, rscale=None, rshift=None, relu=True, o
     """y = act(x*scale + shift (+ res | res*rscale + rshift)).  With ``want_mask`` given the result is a
     pair (y, bits): bits = the sign bits of y, uint8 [L][C/8], when want_mask is true (ReLU only; the
     backward's mask mode 3 reads them instead of y), else None."""
+    _chk(x2d.dim() == 2, "bn_apply: x [L][C]")
     L, C = x2d.shape
+    _bn_c(C, "bn_apply")
+    _chk(L >= 1, f"bn_apply: L={L}")
+    _bn_act(x2d, L, C, "bn_apply: x")
+    _bn_vec(scale, C, "bn_apply: scale")
+    _bn_vec(shift, C, "bn_apply: shift")
+    if res is not None:
+        _bn_act(res, L, C, "bn_apply: res")
+        _chk((rscale is None) == (rshift is None), "bn_apply: rscale and rshift go together")
+        _bn_vec(rscale, C, "bn_apply: rscale", True)
+        _bn_vec(rshift, C, "bn_apply: rshift", True)
+    else:
+        _chk(rscale is None and rshift is None, "bn_apply: rscale / rshift without res")
     if out is None:
         out = torch.empty_like(x2d)
+    else:
+        _bn_act(out, L, C, "bn_apply: out")
     mbits = None
     if want_mask:
         _chk(relu and C % 8 == 0, "bn_apply: mask bits need ReLU and C % 8 == 0")
@@ -650,7 +720,19 @@ def bn_apply(x2d, scale, shift, res=None, rscale=None, rshift=None, relu=True, o
 
 def bn_bwd_reduce(g, x, mean, invstd, mode=0, msrc=None, mscale=None, mshift=None, x2=None, mean2=None,
                   invstd2=None):
+    _chk(x.dim() == 2, "bn_bwd_reduce: x [L][C]")
     L, C = x.shape
+    _bn_c(C, "bn_bwd_reduce")
+    _chk(L >= 1, f"bn_bwd_reduce: L={L}")
+    _bn_act(x, L, C, "bn_bwd_reduce: x")
+    _bn_act(g, L, C, "bn_bwd_reduce: g")
+    _bn_vec(mean, C, "bn_bwd_reduce: mean")
+    _bn_vec(invstd, C, "bn_bwd_reduce: invstd")
+    _bn_mask(mode, msrc, mscale, mshift, L, C, "bn_bwd_reduce")
+    if x2 is not None:
+        _bn_act(x2, L, C, "bn_bwd_reduce: x2")
+        _bn_vec(mean2, C, "bn_bwd_reduce: mean2")
+        _bn_vec(invstd2, C, "bn_bwd_reduce: invstd2")
     slab = stat_bins(C, x.device)
     slab2 = stat_bins(C, x.device) if x2 is not None else None
     call("pdnn_bn_bwd_reduce", ptr(g), ptr(x), L, C, ptr(mean), ptr(invstd), int(mode), ptr(msrc), ptr(mscale),
@@ -660,12 +742,19 @@ def bn_bwd_reduce(g, x, mean, invstd, mode=0, msrc=None, mscale=None, mshift=Non
 
 def bn_bwd_finalize(slab, rows, dgamma=None, dbeta=None, accumulate=False, acc=None):
     """-> (dgamma, dbeta) of this backward; ``acc`` = (gamma.grad, beta.grad) also receive them (+=)."""
+    _bn_slab(slab, rows, "bn_bwd_finalize")
     C = slab.shape[1]
+    ga, ba = acc if acc is not None else (None, None)
+    _chk((ga is None) == (ba is None), "bn_bwd_finalize: acc = (gamma.grad, beta.grad)")
+    _bn_vec(ga, C, "bn_bwd_finalize: acc[0]", True)
+    _bn_vec(ba, C, "bn_bwd_finalize: acc[1]", True)
     if dgamma is None:
+        _chk(dbeta is None and not accumulate, "bn_bwd_finalize: dgamma and dbeta go together")
         dgamma = torch.empty(C, device=slab.device, dtype=F32)
         dbeta = torch.empty_like(dgamma)
-    ga, ba = acc if acc is not None else (None, None)
-    _chk(rows == STAT_BINS and slab.shape[0] == 2 * STAT_BINS, "bn_bwd_finalize: a stat_bins() slab")
+    else:
+        _bn_vec(dgamma, C, "bn_bwd_finalize: dgamma")
+        _bn_vec(dbeta, C, "bn_bwd_finalize: dbeta")
     call("pdnn_bn_bwd_finalize", ptr(slab), rows, C, ptr(dgamma), ptr(dbeta), int(accumulate), ptr(ga), ptr(ba),
          stream())
     _release_bins(slab)
@@ -675,10 +764,34 @@ def bn_bwd_finalize(slab, rows, dgamma=None, dbeta=None, accumulate=False, acc=N
 def bn_bwd_apply(g, x, mean, invstd, gamma, dgamma, dbeta, mode=0, msrc=None, mscale=None, mshift=None,
                  want_dx=True, x2=None, mean2=None, invstd2=None, gamma2=None, dgamma2=None, dbeta2=None,
                  want_gm=False):
+    """-> (dx, dx2, gm).  The kernel exists for: mask modes 0-3 with dx; a second BN (x2 -> dx2) with modes 0, 1, 3;
+    gm (want_gm) with modes 1-3; gm without dx (want_dx=False) with modes 1 and 3 and no second BN."""
+    _chk(x.dim() == 2, "bn_bwd_apply: x [L][C]")
+    L, C = x.shape
+    _bn_c(C, "bn_bwd_apply")
+    _chk(L >= 1, f"bn_bwd_apply: L={L}")
+    _bn_act(x, L, C, "bn_bwd_apply: x")
+    _bn_act(g, L, C, "bn_bwd_apply: g")
+    _bn_vec(mean, C, "bn_bwd_apply: mean")
+    _bn_vec(invstd, C, "bn_bwd_apply: invstd")
+    _bn_vec(gamma, C, "bn_bwd_apply: gamma", True)
+    _bn_vec(dgamma, C, "bn_bwd_apply: dgamma")
+    _bn_vec(dbeta, C, "bn_bwd_apply: dbeta")
+    _bn_mask(mode, msrc, mscale, mshift, L, C, "bn_bwd_apply")
+    _chk(not (want_gm and mode == 0), "bn_bwd_apply: want_gm needs a mask mode (with mode 0 gm is g)")
+    _chk(want_dx or (want_gm and x2 is None and mode in (1, 3)),
+         "bn_bwd_apply: want_dx=False only with want_gm, mask mode 1 or 3 and no x2")
+    if x2 is not None:
+        _chk(mode != 2, "bn_bwd_apply: no second BN with mask mode 2")
+        _bn_act(x2, L, C, "bn_bwd_apply: x2")
+        _bn_vec(mean2, C, "bn_bwd_apply: mean2")
+        _bn_vec(invstd2, C, "bn_bwd_apply: invstd2")
+        _bn_vec(gamma2, C, "bn_bwd_apply: gamma2", True)
+        _bn_vec(dgamma2, C, "bn_bwd_apply: dgamma2")
+        _bn_vec(dbeta2, C, "bn_bwd_apply: dbeta2")
     dx = torch.empty_like(x) if want_dx else None
     dx2 = torch.empty_like(x) if x2 is not None else None
     gm = torch.empty_like(x) if want_gm else None
-    L, C = x.shape
     call("pdnn_bn_bwd_apply", ptr(g), ptr(x), L, C, ptr(mean), ptr(invstd), ptr(gamma), ptr(dgamma), ptr(dbeta),
          int(mode), ptr(msrc), ptr(mscale), ptr(mshift), ptr(dx), ptr(x2), ptr(mean2), ptr(invstd2), ptr(gamma2),
          ptr(dgamma2), ptr(dbeta2), ptr(dx2), ptr(gm), stream())
