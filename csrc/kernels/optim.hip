@@ -154,6 +154,74 @@ __global__ void __launch_bounds__(NT) sumsq_kernel(const float* __restrict__ x, 
     s = block_sum<NT>(s, red);
     if (threadIdx.x == 0) atomicAdd(out, s);
 }
+
+// Global-norm gradient clipping, in two stream-ordered launches that write nothing but a workspace and a 3-float
+// result (the gradient itself is only read; the update kernels above apply the coefficient through gscale_ptr).
+//
+// 1. sumsq_partials_kernel: block b stores the sum of squares of its grid-stride share of g[0, n) to out[b]
+//    (every block stores, nothing to zero; no atomics, so the result depends only on n, the alignment of g and
+//    the grid).  float4 loads over the 16-byte aligned body, four of them in flight per thread into four
+//    accumulators; the <= 3 elements in front of the body and the <= 3 behind it go to block 0's first lanes.
+// 2. clip_coef_kernel: one block adds the partials of all ranges in a fixed order in double and writes
+//    out[0] = norm of the gradient as the update sees it, out[1] = dev * min(1, max_norm / (norm + 1e-6))
+//    (torch.nn.utils.clip_grad_norm_'s formula), out[2] = 1 when the norm is not finite.
+constexpr int CLIP_MAX_PARTS = 8 * 512;     // workspace floats: 8 ranges of at most 512 partials (ops/kernels.py)
+
+__device__ __forceinline__ float sq4(const float4 v, float s) {
+    return s + ((v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w));
+}
+
+__global__ void __launch_bounds__(NT) sumsq_partials_kernel(const float* __restrict__ g, long n,
+                                                            float* __restrict__ out) {
+    __shared__ float red[NT / 64];
+    long head = (long)(((16 - (reinterpret_cast<uintptr_t>(g) & 15)) & 15) >> 2);
+    if (head > n) head = n;
+    const float4* __restrict__ b = reinterpret_cast<const float4*>(g + head);
+    const long n4 = (n - head) >> 2;
+    const long tail = head + 4 * n4;                   // first element behind the body
+    const long stride = (long)gridDim.x * NT;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    long i = (long)blockIdx.x * NT + threadIdx.x;
+    for (; i + 3 * stride < n4; i += 4 * stride) {
+        const float4 v0 = b[i], v1 = b[i + stride], v2 = b[i + 2 * stride], v3 = b[i + 3 * stride];
+        s0 = sq4(v0, s0);
+        s1 = sq4(v1, s1);
+        s2 = sq4(v2, s2);
+        s3 = sq4(v3, s3);
+    }
+    for (; i < n4; i += stride) s0 = sq4(b[i], s0);
+    if (blockIdx.x == 0) {
+        const long t = threadIdx.x;
+        if (t < head) s1 += g[t] * g[t];
+        if (tail + t < n) s2 += g[tail + t] * g[tail + t];
+    }
+    const float s = block_sum<NT>((s0 + s1) + (s2 + s3), red);
+    if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+
+__global__ void __launch_bounds__(NT) clip_coef_kernel(const float* __restrict__ partials, int nparts, float max_norm,
+                                                       float gscale, const float* __restrict__ dev_scale,
+                                                       float* __restrict__ out) {
+    __shared__ double red[NT];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += NT) s += (double)partials[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = NT / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double dev = dev_scale ? (double)*dev_scale : 1.0;
+        const double norm = fabs((double)gscale * dev) * sqrt(red[0]);
+        double c = (double)max_norm / (norm + 1e-6);
+        c = c > 1.0 ? 1.0 : c;                         // a NaN stays a NaN (torch.clamp(max=1) semantics)
+        const float nf = (float)norm;
+        out[0] = nf;
+        out[1] = (float)(dev * c);
+        out[2] = (nf - nf == 0.f) ? 0.f : 1.f;         // inf - inf and NaN - NaN are NaN
+    }
+}
 }  // namespace
 
 PDNN_API int pdnn_sgd_step(float* p, const float* g, float* buf, bf16_t* shadow, long n, float lr, float momentum,
@@ -198,5 +266,28 @@ PDNN_API int pdnn_axpy_f32(float* y, const float* x, long n, float a, hipStream_
 PDNN_API int pdnn_sumsq_f32(const float* x, long n, float* out, hipStream_t st) {
     hipLaunchKernelGGL(sumsq_kernel, dim3(stream_grid(n, NT) > 512 ? 512 : stream_grid(n, NT)), dim3(NT), 0, st, x, n,
                        out);
+    PDNN_LAUNCH_RET;
+}
+
+// Sum-of-squares partials of g[0, n) into partials[part_off ...]; `partials` is a workspace of CLIP_MAX_PARTS
+// floats.  Returns the number of partials written (>= 1; n == 0 writes one 0), or -hipError: nothing is launched
+// for a null or misaligned pointer, a negative n, or a part_off whose partials would not fit the workspace.
+PDNN_API int pdnn_sumsq_partials(const float* g, long n, float* partials, int part_off, hipStream_t st) {
+    if (g == nullptr || partials == nullptr || n < 0 || part_off < 0) return -(int)hipErrorInvalidValue;
+    if ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(partials)) & 3) return -(int)hipErrorInvalidValue;
+    const unsigned grid = stream_grid(n / 4 + 1, NT);              // <= 512
+    if ((long)part_off + grid > CLIP_MAX_PARTS) return -(int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(sumsq_partials_kernel, dim3(grid), dim3(NT), 0, st, g, n, partials + part_off);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? (int)grid : -(int)e;
+}
+
+// out[0..2] = {norm, clip coefficient, non-finite flag} from the first nparts workspace partials (see above);
+// dev_scale may be null (1).  The update kernels take out + 1 as gscale_ptr.
+PDNN_API int pdnn_clip_coef(const float* partials, int nparts, float max_norm, float gscale, const float* dev_scale,
+                            float* out, hipStream_t st) {
+    if (partials == nullptr || out == nullptr || nparts < 1 || nparts > CLIP_MAX_PARTS)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(NT), 0, st, partials, nparts, max_norm, gscale, dev_scale, out);
     PDNN_LAUNCH_RET;
 }

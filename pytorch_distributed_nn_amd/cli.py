@@ -7,6 +7,7 @@ S4 tf flags).  All reference flag names and defaults are accept
 New:  --mode ddp|ps|single (default: ps when --comm-type is Bcast/Async and world > 1, i.e. the
 reference's behaviour; ddp when --comm-type AllReduce), --comm-type AllReduce, --bucket-cap-mb,
 --dtype bf16|fp32|fp8, --synthetic, --data-dir, --max-steps, --optimizer sgd|adam|adamw, --weight-decay,
+--grad-clip NORM (global L2 norm, fused into the optimizer step; 0 = off), --opt-overlap (DDP per-bucket updates),
 --n-to-collect (backup workers), --interval-ms, --no-shortcircuit, --evaluator,
 --inject-straggler RANK:MS[,RANK:MS], --straggler-mode (k-of-n inside DDP), --checkpoint-dir, --resume,
 --trace FILE, --metrics FILE.
@@ -46,6 +47,12 @@ def add_fit_args(p: argparse.ArgumentParser):
     p.add_argument("--max-steps", type=int, default=None)
     p.add_argument("--optimizer", type=str, default="sgd", choices=["sgd", "adam", "adamw"])
     p.add_argument("--weight-decay", type=float, default=0.0)
+    p.add_argument("--grad-clip", type=float, default=0.0, metavar="NORM",
+                   help="clip the gradient to this global L2 norm before the update (0 = off); the fused optimizers "
+                        "do it inside their step, one read of the flat gradient (optim/fused.py set_grad_clip)")
+    p.add_argument("--opt-overlap", action="store_true",
+                   help="DDP: apply each bucket's optimizer update right after its all-reduce, beside the rest of "
+                        "the backward (DistributedDataParallel.overlap_optimizer); not with --grad-clip")
     # exponential staircase decay (TF trainer, distributed_TF/src/distributed_train.py:143-147):
     # lr = lr0 * factor ** floor(step / (steps_per_epoch * epochs_per_decay))
     p.add_argument("--lr-decay-factor", type=float, default=1.0)
@@ -104,13 +111,19 @@ def parse_args(argv=None):
                 raise SystemExit(f"{pre.config}: unknown option {k!r}")
             defaults[dest] = v
         p.set_defaults(**defaults)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.grad_clip < 0:
+        raise SystemExit("--grad-clip must be >= 0 (0 = off)")
+    if args.grad_clip and args.opt_overlap:
+        raise SystemExit("--grad-clip cannot be combined with --opt-overlap: the overlapped optimizer updates each "
+                         "bucket during the backward, before the gradient's global norm exists")
+    return args
 
 
 # flags each mode does not use: given explicitly (or by a YAML config) with a non-default value they are an
 # error, never silently dropped (a PS sweep config that says "optimizer: adam" must run Adam or fail)
 _PS_IGNORED = ("graph", "straggler_mode", "resume", "watchdog_timeout", "inject_hang", "trace", "metrics",
-               "num_workers", "checkpoint_interval")
+               "num_workers", "checkpoint_interval", "grad_clip", "opt_overlap")
 _COLLECTIVE_IGNORED = ("evaluator", "eval_interval", "no_shortcircuit", "save_model_secs", "ps_workers")
 _STRAGGLER_ONLY = ("n_to_collect", "interval_ms", "num_aggregate")
 
@@ -130,6 +143,8 @@ def check_mode_flags(args, mode: str, world: int):
             bad += [k for k in _STRAGGLER_ONLY if k in given]
         if mode == "single" and "straggler_mode" in given:
             bad.append("straggler_mode")
+        if mode == "single" and "opt_overlap" in given:
+            bad.append("opt_overlap")
     if bad:
         flags = ", ".join("--" + k.replace("_", "-") for k in sorted(set(bad)))
         raise SystemExit(f"--mode {mode} (world size {world}) does not use {flags}: remove them or pick the mode "
@@ -239,6 +254,10 @@ def main(argv=None):
         opt = AdamW(params, lr=args.lr, weight_decay=args.weight_decay)
     if isinstance(net, DistributedDataParallel):
         net.attach_optimizer(opt)
+        if args.opt_overlap and net.overlap_optimizer(opt) is None and rank == 0:
+            print("--opt-overlap: this optimizer / bucket layout does not qualify, updating after the backward")
+    elif args.opt_overlap:
+        raise SystemExit("--opt-overlap needs --mode ddp with communication (world size > 1)")
     strag = parse_stragglers(args.inject_straggler)
     if rank in strag:
         import time as _t
@@ -289,6 +308,7 @@ def main(argv=None):
     tr = Trainer(net, opt, OF.cross_entropy, dev, rank, world, args.log_interval, args.metrics,
                  args.trace, args.checkpoint_dir, arch=args.network, printer=print if rank == 0 else (lambda *a: None),
                  graph=graph, checkpoint_interval=args.checkpoint_interval, watchdog=wd, lr_schedule=lr_schedule,
+                 grad_clip=args.grad_clip or None,
                  compute_log=(os.path.join(args.out_dir, f"compute_times_rank{rank}.jsonl")
                               if args.compute_times else None))
     if args.resume:

@@ -115,6 +115,8 @@ _SIGS = {
     "pdnn_scale_f32": [P, L, F, P, I, P],
     "pdnn_axpy_f32": [P, P, L, F, P],
     "pdnn_sumsq_f32": [P, L, P, P],
+    "pdnn_sumsq_partials": [P, L, P, I, P],          # returns the number of partials, or -hipError
+    "pdnn_clip_coef": [P, I, F, F, P, P, P],
     "pdnn_act_fwd": [P, P, L, I, P],
     "pdnn_act_bwd": [P, P, P, L, I, P],
     "pdnn_add": [P, P, P, L, F, F, P],

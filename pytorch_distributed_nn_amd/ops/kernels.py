@@ -11,7 +11,7 @@ import ctypes
 
 import torch
 
-from ._backend import _CUR_DEV, call, lib, ptr, stream
+from ._backend import _CUR_DEV, HipError, call, lib, ptr, stream
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -1119,6 +1119,47 @@ def axpy_(y, x, a):
 
 def sumsq(x, out):
     call("pdnn_sumsq_f32", ptr(x), x.numel(), ptr(out), stream())
+    return out
+
+
+# Global-norm gradient clipping (optim.hip): sum-of-squares partials per flat range into one workspace, then one
+# block turns them into [norm, clip coefficient, non-finite flag].  The workspace holds up to CLIP_RANGES ranges
+# of CLIP_PARTS partials (CLIP_MAX_PARTS in optim.hip).
+CLIP_RANGES = 8
+CLIP_PARTS = 512
+CLIP_WS = CLIP_RANGES * CLIP_PARTS
+
+
+def _clip_f32(t, n, name):
+    _chk(t is not None and t.dtype == F32 and t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.numel() >= n,
+         f"{name}: expected a contiguous CUDA fp32 vector of at least {n}")
+
+
+def sumsq_partials(g, ws, part_off=0):
+    """Deterministic sum-of-squares partials of the flat fp32 gradient ``g`` into ``ws[part_off:]``; returns how
+    many partials were written (at most CLIP_PARTS).  ``ws`` is the CLIP_WS-float workspace."""
+    _clip_f32(g, 0, "sumsq_partials: g")
+    _clip_f32(ws, CLIP_WS, "sumsq_partials: workspace")
+    _chk(g.device == ws.device, "sumsq_partials: g and workspace on different devices")
+    nblk = min(max((g.numel() // 4 + 1 + 255) // 256, 1), CLIP_PARTS)
+    _chk(0 <= part_off and part_off + nblk <= CLIP_WS,
+         f"sumsq_partials: part_off={part_off} + {nblk} partials exceed the workspace ({CLIP_WS})")
+    rc = lib().pdnn_sumsq_partials(ptr(g), g.numel(), ptr(ws), int(part_off), stream())
+    if rc < 0:
+        raise HipError(f"pdnn_sumsq_partials failed with hipError {-rc}")
+    return rc
+
+
+def clip_coef(ws, nparts, max_norm, out, gscale=1.0, dev_scale=None):
+    """``out[0:3]`` = [norm, clip coefficient, non-finite flag] from ``ws[:nparts]``: norm = |gscale * dev| *
+    sqrt(sum), coefficient = dev * min(1, max_norm / (norm + 1e-6)), dev = ``dev_scale[0]`` (1 when None)."""
+    _clip_f32(ws, CLIP_WS, "clip_coef: workspace")
+    _clip_f32(out, 3, "clip_coef: out")
+    _chk(1 <= nparts <= CLIP_WS, f"clip_coef: nparts={nparts}")
+    if dev_scale is not None:
+        _chk(dev_scale.dtype == F32 and dev_scale.is_cuda and dev_scale.numel() >= 1,
+             "clip_coef: dev_scale must be a CUDA fp32 scalar")
+    call("pdnn_clip_coef", ptr(ws), int(nparts), float(max_norm), float(gscale), ptr(dev_scale), ptr(out), stream())
     return out
 
 

@@ -8,6 +8,8 @@ When a param group covers a contiguous range of a :class:`~.flat.FlatParams` are
 (``optim.hip``) that also refreshes the bf16 weight shadow and applies the gradient averaging factor
 (``grad_scale``, or a device-side scale such as 1/alive-count for the straggler-tolerant modes).  Groups
 that are not flat fall back to one launch per tensor (GPU) or the torch reference update (CPU).
+``set_grad_clip(max_norm)`` adds global-norm gradient clipping to the same step: two norm launches leave the
+clip coefficient in device memory and the update launch applies it (the gradient buffer is not rewritten).
 
 Reference parity: the PS master applies ``param -= lr * avg_grad`` (sync_replicas_master_nn.py:22-28,
 216-219) and ignores --momentum (defect D9); the C++ master fuses the average into the update as
@@ -42,11 +44,84 @@ class _FusedBase(torch.optim.Optimizer):
         self._flat_cache = {}
         self._graph = False            # graph mode: per-step hyper-parameters live in device memory
         self._hyper = {}
+        self._clip = None              # set_grad_clip(): max global L2 norm of the gradient, None = off
+        self._clip_out = None          # [norm, coefficient, non-finite flag], written by every clipped step()
+        self._clip_ws = None           # the norm kernel's partials (GPU only)
 
     def _group_flat(self, gi, group):
         if gi not in self._flat_cache:
             self._flat_cache[gi] = _flat_of(group["params"])
         return self._flat_cache[gi]
+
+    # ------------------------------------------------------------------------------- gradient clipping
+    def set_grad_clip(self, max_norm: float | None):
+        """Clip the gradient to a global L2 norm of ``max_norm`` inside ``step()``; ``None`` or 0 turns it off
+        (the step is then exactly the unclipped one).
+
+        The norm is taken over every param group (and arena) of this optimizer, of the gradient as the update
+        sees it (times ``grad_scale`` and ``grad_scale_dev``), with ``torch.nn.utils.clip_grad_norm_``'s formula
+        ``coef = min(1, max_norm / (norm + 1e-6))``.  Unlike torch's in-place clip the gradient buffer is NOT
+        modified: a norm kernel reads it once and writes the coefficient to device memory, and the fused update
+        kernels apply it through the device scale they already read.  No host sync, capturable in a hipGraph.
+        Groups that are not flat ranges on a GPU (CPU arenas, loose tensors, more than 8 ranges) compute the same
+        formula with torch ops.  ``grad_norm`` / ``grad_nonfinite`` hold the last step's norm and whether it was
+        inf/NaN (the step is not skipped then: the coefficient is what the formula gives, as torch with
+        ``error_if_nonfinite=False``)."""
+        self._clip = float(max_norm) if max_norm else None
+        if self._clip is not None:
+            self._clip_alloc()
+
+    def _clip_alloc(self):
+        # outside any graph capture (set_grad_clip / graph_mode), for the reason _hyper is: a buffer created inside
+        # a capture belongs to the graph's pool
+        if self._clip_out is not None:
+            return
+        from ..ops.kernels import CLIP_WS
+        dev = self.param_groups[0]["params"][0].device
+        self._clip_out = torch.zeros(3, dtype=torch.float32, device=dev)
+        if dev.type == "cuda":
+            self._clip_ws = torch.zeros(CLIP_WS, dtype=torch.float32, device=dev)
+
+    @property
+    def grad_norm(self):
+        """Device scalar: the clipped step's global gradient norm (None before clipping was ever set)."""
+        return None if self._clip_out is None else self._clip_out[0]
+
+    @property
+    def grad_nonfinite(self):
+        """Device scalar: 1.0 when the last clipped step's norm was inf or NaN, else 0.0."""
+        return None if self._clip_out is None else self._clip_out[2]
+
+    @torch.no_grad()
+    def _clip_scale(self):
+        """The device gradient scale of this step's update kernels: ``grad_scale_dev`` without clipping, else the
+        clip coefficient (with ``grad_scale_dev`` folded in), computed here from the current gradients."""
+        if self._clip is None:
+            return self.grad_scale_dev
+        from ..ops.kernels import CLIP_RANGES
+        out = self._clip_out
+        flats = [self._group_flat(gi, g) for gi, g in enumerate(self.param_groups)]
+        if (self._clip_ws is not None and len(flats) <= CLIP_RANGES
+                and all(fp is not None and fp.grad.device == out.device for fp, _ in flats)):
+            from ..ops import kernels as K
+            nparts = 0
+            for fp, (s, e) in flats:
+                nparts += K.sumsq_partials(fp.grad[s:e], self._clip_ws, nparts)
+            K.clip_coef(self._clip_ws, nparts, self._clip, out, self.grad_scale, self.grad_scale_dev)
+            return out[1:2]
+        norms = []
+        for (fp, rng), group in zip(flats, self.param_groups):
+            # what the group's update will read: the arena range (fused launch) or the parameters' own .grad
+            gs = ([fp.grad[rng[0]:rng[1]]] if fp is not None and fp.data.is_cuda
+                  else [p.grad for p in group["params"] if p.grad is not None])
+            norms += [torch.linalg.vector_norm(g).to(out.device) for g in gs]
+        dev = self.grad_scale_dev.to(out.device).reshape(()) if self.grad_scale_dev is not None else 1.0
+        norm = torch.linalg.vector_norm(torch.stack(norms)) if norms else torch.zeros((), device=out.device)
+        norm = norm * abs(self.grad_scale * dev)
+        out[0] = norm
+        out[1] = dev * torch.clamp(self._clip / (norm + 1e-6), max=1.0)
+        out[2] = (~torch.isfinite(norm)).float()
+        return out[1:2]
 
     # ---------------------------------------------------------------------------------- graph mode
     # A hipGraph captured around ``step()`` replays the kernels with the arguments they had at capture.
@@ -68,6 +143,8 @@ class _FusedBase(torch.optim.Optimizer):
                 if gi not in self._hyper:
                     self._hyper[gi] = torch.zeros(self._HYPER_LEN, dtype=torch.float32, device=fp.data.device)
                     self._fill_hyper(gi, group, advance=False)
+            if self._clip is not None:
+                self._clip_alloc()
         self._graph = bool(on)
 
     def _check_graphable(self, gi):
@@ -98,6 +175,8 @@ class _FusedBase(torch.optim.Optimizer):
     # arena, eager (not graph) mode.
     def _overlap_ok(self):
         if self._graph or len(self.param_groups) != 1:
+            return None
+        if self._clip is not None:     # a per-bucket update cannot know the global norm
             return None
         fp, rng = self._group_flat(0, self.param_groups[0])
         if fp is None or not fp.data.is_cuda:
@@ -186,6 +265,7 @@ class SGD(_FusedBase):
                 loss = closure()
         if self._consume_overlap():
             return loss
+        gsd = self._clip_scale()
         for gi, group in enumerate(self.param_groups):
             lr, mom, damp, wd, nest = (group["lr"], group["momentum"], group["dampening"], group["weight_decay"],
                                        group["nesterov"])
@@ -200,7 +280,7 @@ class SGD(_FusedBase):
                 buf = st.get("momentum_buffer")
                 hyper = self._hyper_buf(gi, 1, fp.data.device) if self._graph else None
                 K.sgd_step(fp.data[s:e], fp.grad[s:e], buf, fp.shadow[s:e] if fp.shadow is not None else None,
-                           lr, mom, damp, wd, nest, self.grad_scale_dev, self.grad_scale, first, hyper=hyper)
+                           lr, mom, damp, wd, nest, gsd, self.grad_scale, first, hyper=hyper)
                 fp.generation += 1
                 continue
             for p in group["params"]:
@@ -209,8 +289,8 @@ class SGD(_FusedBase):
                 g = p.grad
                 if self.grad_scale != 1.0:
                     g = g * self.grad_scale
-                if self.grad_scale_dev is not None:
-                    g = g * self.grad_scale_dev
+                if gsd is not None:
+                    g = g * gsd.to(g.device)
                 if wd != 0:
                     g = g.add(p, alpha=wd)
                 if mom != 0:
@@ -269,6 +349,7 @@ class Adam(_FusedBase):
                 loss = closure()
         if self._consume_overlap():
             return loss
+        gsd = self._clip_scale()
         for gi, group in enumerate(self.param_groups):
             lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
             fp, rng = self._group_flat(gi, group)
@@ -288,16 +369,15 @@ class Adam(_FusedBase):
                 t = max(st["step"], 1)
                 K.adam_step(fp.data[s:e], fp.grad[s:e], st["exp_avg"], st["exp_avg_sq"],
                             fp.shadow[s:e] if fp.shadow is not None else None, lr, b1, b2, eps, wd,
-                            self.decoupled, 1 - b1 ** t, 1 - b2 ** t, self.grad_scale_dev, self.grad_scale,
-                            hyper=hyper)
+                            self.decoupled, 1 - b1 ** t, 1 - b2 ** t, gsd, self.grad_scale, hyper=hyper)
                 fp.generation += 1
                 continue
             for p in group["params"]:
                 if p.grad is None:
                     continue
                 g = p.grad * self.grad_scale
-                if self.grad_scale_dev is not None:
-                    g = g * self.grad_scale_dev
+                if gsd is not None:
+                    g = g * gsd.to(g.device)
                 st = self.state[p]
                 if "step" not in st:
                     st["step"] = 0

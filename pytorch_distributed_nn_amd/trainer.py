@@ -126,12 +126,25 @@ class Trainer:
                 # the optimizer already ran per bucket inside the backward (DistributedDataParallel.
                 # overlap_optimizer): clipping now would be silently skipped
                 raise ValueError("grad_clip cannot be combined with DistributedDataParallel.overlap_optimizer")
-            torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.grad_clip)
+            if hasattr(self.opt, "set_grad_clip"):
+                # fused optimizers clip inside step(): one read of the flat gradient, the coefficient applied
+                # by the update kernel (optim/fused.py set_grad_clip)
+                self.opt.set_grad_clip(self.grad_clip)
+            else:
+                self._torch_norm = torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.grad_clip)
         with self._span("optimizer"):
             self.opt.step()
         m3 = self._mark()
         self.step_no += 1
         return loss, out, (m0, m1, m2, m3)
+
+    def _grad_norm(self):
+        """The last step's global gradient norm (a tensor) when ``grad_clip`` is on, else None."""
+        if not self.grad_clip:
+            return None
+        if hasattr(self.opt, "set_grad_clip"):
+            return self.opt.grad_norm
+        return getattr(self, "_torch_norm", None)
 
     # ----------------------------------------------------------------------------------------- loops
     def _finish(self, pend):
@@ -191,6 +204,9 @@ class Trainer:
                         raise FloatingPointError(f"Model diverged with loss = {lv} at step {self.step_no}")
                     p1 = float(accuracy(out.detach(), y, (1,))[0]) if out.dim() == 2 else float("nan")
                     rec["loss"], rec["prec1"] = lv, p1
+                    gn = self._grad_norm()
+                    if gn is not None:           # read where the loss is: no sync point of its own
+                        rec["grad_norm"] = float(gn)
                 if log_now:          # once this step has completed on the device: a wall-clock point of the run
                     if not isinstance(marks[-1], float):
                         marks[-1].synchronize()

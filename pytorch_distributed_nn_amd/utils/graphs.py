@@ -69,7 +69,12 @@ class GraphedStep:
         loss, out = self._fwd(x, y)
         loss.backward()
         if self.grad_clip:           # device-side norm + clamp: no host sync, capturable
-            torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.grad_clip, foreach=True)
+            if hasattr(self.opt, "set_grad_clip"):
+                # fused optimizers: two norm launches inside step(), coefficient applied by the update kernel
+                # (its buffers exist by now: the warm-up steps and graph_mode() allocate them before a capture)
+                self.opt.set_grad_clip(self.grad_clip)
+            else:
+                torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.grad_clip, foreach=True)
         self.opt.step()
         # Only DETACHED results leave a step: a live autograd graph from an eager step (held by a returned
         # loss/logits) keeps the parameters' AccumulateGrad nodes, created on the eager stream, alive into
