@@ -627,7 +627,7 @@ static dim3 attn_grid(int ntile, int H, int B) {
 // qkv [B*T][3*H*64] bf16 -> out [B*T][H*64] bf16, lse2 [B][H][T] fp32.  T % 128 == 0.
 PDNN_API int pdnn_flash_attn_fwd(const bf16_t* qkv, bf16_t* out, float* lse2, int B, int T, int H, float scale,
                                  int causal, hipStream_t st) {
-    if (T % 128) return (int)hipErrorInvalidValue;
+    if (B < 1 || T < 1 || H < 1 || T % 128 || !qkv || !out || !lse2) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(attn_fwd_kernel, attn_grid(T / 128, H, B), dim3(NTA), 0, st, qkv, out, lse2, T, H, scale, causal);
     PDNN_LAUNCH_RET;
 }
@@ -646,7 +646,8 @@ static void launch_dkdv(const bf16_t* qkv, const bf16_t* dO, const float* lse2, 
 PDNN_API int pdnn_flash_attn_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dO, const float* lse2,
                                  float* delta, bf16_t* dqkv, int B, int T, int H, float scale, int causal,
                                  hipStream_t st) {
-    if (T % 128) return (int)hipErrorInvalidValue;
+    if (B < 1 || T < 1 || H < 1 || T % 128 || !qkv || !out || !dO || !lse2 || !delta || !dqkv)
+        return (int)hipErrorInvalidValue;
     const bool wq = pg::tune().attn_bwd_wide & 1;
     if (pg::tune().attn_delta_in_dq) {       // dQ first (it writes delta), then dK / dV
         if (wq)

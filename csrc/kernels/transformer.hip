@@ -166,7 +166,7 @@ __global__ void __launch_bounds__(NT) layernorm_bwd_kernel(const bf16_t* __restr
 
 // ---------------------------------------------------------------------------------------------- softmax
 // P[r][k] = softmax_k(S[r][k] * scale) over k <= q (causal, q = r % T), 0 elsewhere; lse[r] saved.
-// One wave per row, T <= 64 * 32.
+// One wave per row; a lane takes 4 keys per stride of 256, any T % 4 == 0.
 __global__ void __launch_bounds__(NT) attn_softmax_fwd_kernel(const float* __restrict__ S, long ldS,
                                                               bf16_t* __restrict__ P, long ldP,
                                                               float* __restrict__ lse, int rows, int T, float scale,
@@ -286,8 +286,8 @@ __global__ void __launch_bounds__(NT) embedding_bwd_kernel(const int64_t* __rest
 
 PDNN_API int pdnn_layernorm_fwd(const bf16_t* x, const float* g, const float* b, bf16_t* y, float* mean, float* rstd,
                                 int rows, int D, float eps, hipStream_t st) {
+    if (rows < 1 || D < 8 || D % 8 || D > 2048) return (int)hipErrorInvalidValue;
     const dim3 grid((rows + 3) / 4);
-    if (D % 8 || D > 2048) return (int)hipErrorInvalidValue;
     if (D <= 512)
         hipLaunchKernelGGL(layernorm_fwd_kernel<1>, grid, dim3(NT), 0, st, x, g, b, y, mean, rstd, rows, D, eps);
     else if (D <= 1024)
@@ -302,7 +302,7 @@ PDNN_API int pdnn_layernorm_bwd_blocks(int rows) { return rows / 16 < 1 ? 1 : (r
 PDNN_API int pdnn_layernorm_bwd(const bf16_t* dy, const bf16_t* x, const float* g, const float* mean,
                                 const float* rstd, const bf16_t* dres, bf16_t* dx, float* slab, int rows, int D,
                                 int nblocks, hipStream_t st) {
-    if (D % 8 || D > 2048) return (int)hipErrorInvalidValue;
+    if (rows < 1 || nblocks < 1 || D < 8 || D % 8 || D > 2048) return (int)hipErrorInvalidValue;
     const dim3 grid(nblocks);
     if (D <= 512)
         hipLaunchKernelGGL(layernorm_bwd_kernel<1>, grid, dim3(NT), 0, st, dy, x, g, mean, rstd, dres, dx, slab, rows, D);

@@ -1196,8 +1196,11 @@ def gemm_nt_ex(x, w, bias=None, act=0, aux=None, res=None, dgelu=None, w_kn=Fals
 
 def layernorm_fwd(x, g, b, eps):
     _bf16_c(x, "layernorm.x")
+    _chk(x.dim() == 2, "layernorm: x must be 2-D")
     R, D = x.shape
-    _chk(D % 8 == 0 and D <= 2048, f"layernorm: D={D}")
+    _chk(R >= 1 and D >= 8 and D % 8 == 0 and D <= 2048, f"layernorm: rows={R} D={D}")
+    for t, name in ((g, "gamma"), (b, "beta")):
+        _chk(t.dtype == F32 and t.shape == (D,) and t.is_contiguous(), f"layernorm: {name} must be contiguous fp32 [{D}]")
     y = torch.empty_like(x)
     mean = torch.empty(R, device=x.device, dtype=F32)
     rstd = torch.empty_like(mean)
@@ -1208,9 +1211,17 @@ def layernorm_fwd(x, g, b, eps):
 def layernorm_bwd(dy, x, g, mean, rstd, dres=None, acc=None):
     """-> dx (+dres), dgamma, dbeta; with ``acc`` = (gamma.grad, beta.grad) the parameter gradients are
     accumulated there instead (returns dx, None, None)."""
+    _bf16_c(x, "layernorm_bwd.x")
+    _chk(x.dim() == 2, "layernorm_bwd: x must be 2-D")
     R, D = x.shape
+    _chk(R >= 1 and D >= 8 and D % 8 == 0 and D <= 2048, f"layernorm_bwd: rows={R} D={D}")
     dy = dy.contiguous()
-    _chk(dy.shape == x.shape and (dres is None or dres.shape == x.shape), "layernorm_bwd: shapes")
+    _chk(dy.dtype == BF16 and dy.shape == x.shape, "layernorm_bwd: dy must be bf16 of x's shape")
+    _chk(dres is None or (dres.dtype == BF16 and dres.shape == x.shape and dres.is_contiguous()),
+         "layernorm_bwd: dres must be contiguous bf16 of x's shape")
+    _chk(g.dtype == F32 and g.shape == (D,) and g.is_contiguous(), f"layernorm_bwd: gamma must be contiguous fp32 [{D}]")
+    for t, name in ((mean, "mean"), (rstd, "rstd")):
+        _chk(t.dtype == F32 and t.shape == (R,) and t.is_contiguous(), f"layernorm_bwd: {name} must be contiguous fp32 [{R}]")
     nb = lib().pdnn_layernorm_bwd_blocks(R)
     slab = stat_bins(D, x.device)
     dx = torch.empty_like(x)
@@ -1239,7 +1250,8 @@ def attn_softmax_bwd(P, dP, dS, rows, T, scale, causal=False):
 def flash_attn_fwd(qkv, B, T, H, scale, causal=True):
     """Fused attention, head dim 64: qkv [B*T][3*H*64] -> (out [B*T][H*64], lse2 [B][H][T])."""
     _bf16_c(qkv, "flash_attn.qkv")
-    _chk(qkv.shape == (B * T, 3 * H * 64) and T % 128 == 0, f"flash_attn: qkv {tuple(qkv.shape)} B={B} T={T} H={H}")
+    _chk(B >= 1 and T >= 1 and H >= 1 and qkv.shape == (B * T, 3 * H * 64) and T % 128 == 0,
+         f"flash_attn: qkv {tuple(qkv.shape)} B={B} T={T} H={H}")
     out = torch.empty(B * T, H * 64, device=qkv.device, dtype=BF16)
     lse2 = torch.empty(B, H, T, device=qkv.device, dtype=F32)
     call("pdnn_flash_attn_fwd", ptr(qkv), ptr(out), ptr(lse2), B, T, H, float(scale), int(causal), stream())
@@ -1247,8 +1259,15 @@ def flash_attn_fwd(qkv, B, T, H, scale, causal=True):
 
 
 def flash_attn_bwd(qkv, out, dout, lse2, B, T, H, scale, causal=True):
+    _bf16_c(qkv, "flash_attn_bwd.qkv")
+    _chk(B >= 1 and T >= 1 and H >= 1 and qkv.shape == (B * T, 3 * H * 64) and T % 128 == 0,
+         f"flash_attn_bwd: qkv {tuple(qkv.shape)} B={B} T={T} H={H}")
     dout = dout.contiguous()
-    _chk(dout.shape == out.shape and lse2.shape == (B, H, T), "flash_attn_bwd: shapes")
+    _chk(out.dtype == BF16 and out.shape == (B * T, H * 64) and out.is_contiguous(),
+         "flash_attn_bwd: out must be contiguous bf16 [B*T][H*64]")
+    _chk(dout.dtype == BF16 and dout.shape == out.shape, "flash_attn_bwd: dout must be bf16 of out's shape")
+    _chk(lse2.dtype == F32 and lse2.shape == (B, H, T) and lse2.is_contiguous(),
+         "flash_attn_bwd: lse2 must be contiguous fp32 [B][H][T]")
     dqkv = torch.empty_like(qkv)
     delta = torch.empty(B, H, T, device=qkv.device, dtype=F32)
     call("pdnn_flash_attn_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse2), ptr(delta), ptr(dqkv), B, T, H, float(scale),
