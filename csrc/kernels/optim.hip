@@ -10,6 +10,7 @@
 // bf16 compute shadow of the weights that the MFMA kernels read, and folds the gradient averaging
 // factor (1/world, or 1/alive-count for k-of-n straggler mode) in as `gscale` read from device memory.
 #include "common.h"
+#include "optim_update.h"
 
 //
 // Graph replay: a captured hipGraph bakes kernel arguments in, so the per-step hyper-parameters that
@@ -40,11 +41,7 @@ __global__ void __launch_bounds__(NT) sgd_kernel(float* __restrict__ p, const fl
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float d = ga[j] * gs + wd * pa[j];
-            if (momentum != 0.f) {
-                ba[j] = first ? d : momentum * ba[j] + (1.f - dampening) * d;
-                d = nesterov ? d + momentum * ba[j] : ba[j];
-            }
+            const float d = sgd_momentum(ga[j] * gs + wd * pa[j], ba[j], momentum, dampening, nesterov, first);
             pa[j] -= lr * d;
         }
         reinterpret_cast<float4*>(p)[i] = make_float4(pa[0], pa[1], pa[2], pa[3]);
@@ -58,9 +55,9 @@ __global__ void __launch_bounds__(NT) sgd_kernel(float* __restrict__ p, const fl
     for (long i = n4 * 4 + (long)blockIdx.x * NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {
         float d = g[i] * gs + wd * p[i];
         if (momentum != 0.f) {
-            const float b = first ? d : momentum * buf[i] + (1.f - dampening) * d;
+            float b = first ? 0.f : buf[i];
+            d = sgd_momentum(d, b, momentum, dampening, nesterov, first);
             buf[i] = b;
-            d = nesterov ? d + momentum * b : b;
         }
         p[i] -= lr * d;
         if (shadow) shadow[i] = f2bf(p[i]);
@@ -77,9 +74,8 @@ struct AdamCoef {
         gi *= gs;
         if (decoupled) pi -= lr * wd * pi;
         else gi += wd * pi;
-        mi = b1 * mi + (1.f - b1) * gi;
-        vi = b2 * vi + (1.f - b2) * gi * gi;
-        pi -= step * mi / (sqrtf(vi) * rbc2 + eps);
+        adam_moments(gi, mi, vi, b1, b2, 1.f - b1, 1.f - b2);
+        pi -= step * mi / adam_denom(vi, rbc2, eps);
     }
 };
 

@@ -6,7 +6,10 @@ S4 tf flags).  All reference flag names and defaults are accept
 
 New:  --mode ddp|ps|single (default: ps when --comm-type is Bcast/Async and world > 1, i.e. the
 reference's behaviour; ddp when --comm-type AllReduce), --comm-type AllReduce, --bucket-cap-mb,
---dtype bf16|fp32|fp8, --synthetic, --data-dir, --max-steps, --optimizer sgd|adam|adamw, --weight-decay,
+--dtype bf16|fp32|fp8, --synthetic, --data-dir, --max-steps, --optimizer sgd|adam|adamw|lars|lamb, --weight-decay,
+--trust-coef ETA (lars; lars and lamb scale each tensor's step by a trust ratio ||w|| / ||update|| and leave 1-D
+parameters, biases and normalisation gains, out of the scaling and out of weight decay; not in PS mode, whose master
+applies its own fused SGD / Adam, and not with --opt-overlap's per-bucket update),
 --grad-clip NORM (global L2 norm, fused into the optimizer step; 0 = off), --opt-overlap (DDP per-bucket updates),
 --n-to-collect (backup workers), --interval-ms, --no-shortcircuit, --evaluator,
 --inject-straggler RANK:MS[,RANK:MS], --straggler-mode (k-of-n inside DDP), --checkpoint-dir, --resume,
@@ -45,7 +48,9 @@ def add_fit_args(p: argparse.ArgumentParser):
     p.add_argument("--synthetic", action="store_true")
     p.add_argument("--data-dir", type=str, default=None)
     p.add_argument("--max-steps", type=int, default=None)
-    p.add_argument("--optimizer", type=str, default="sgd", choices=["sgd", "adam", "adamw"])
+    p.add_argument("--optimizer", type=str, default="sgd", choices=["sgd", "adam", "adamw", "lars", "lamb"])
+    p.add_argument("--trust-coef", type=float, default=1e-3, metavar="ETA",
+                   help="--optimizer lars: the trust coefficient eta of r = eta |w| / (|g| + wd |w| + eps)")
     p.add_argument("--weight-decay", type=float, default=0.0)
     p.add_argument("--grad-clip", type=float, default=0.0, metavar="NORM",
                    help="clip the gradient to this global L2 norm before the update (0 = off); the fused optimizers "
@@ -117,13 +122,15 @@ def parse_args(argv=None):
     if args.grad_clip and args.opt_overlap:
         raise SystemExit("--grad-clip cannot be combined with --opt-overlap: the overlapped optimizer updates each "
                          "bucket during the backward, before the gradient's global norm exists")
+    if args.trust_coef != 1e-3 and args.optimizer != "lars":
+        raise SystemExit(f"--trust-coef belongs to --optimizer lars (--optimizer {args.optimizer} has no such factor)")
     return args
 
 
 # flags each mode does not use: given explicitly (or by a YAML config) with a non-default value they are an
 # error, never silently dropped (a PS sweep config that says "optimizer: adam" must run Adam or fail)
 _PS_IGNORED = ("graph", "straggler_mode", "resume", "watchdog_timeout", "inject_hang", "trace", "metrics",
-               "num_workers", "checkpoint_interval", "grad_clip", "opt_overlap")
+               "num_workers", "checkpoint_interval", "grad_clip", "opt_overlap", "trust_coef")
 _COLLECTIVE_IGNORED = ("evaluator", "eval_interval", "no_shortcircuit", "save_model_secs", "ps_workers")
 _STRAGGLER_ONLY = ("n_to_collect", "interval_ms", "num_aggregate")
 
@@ -132,9 +139,12 @@ def check_mode_flags(args, mode: str, world: int):
     """Raise SystemExit naming every flag the chosen mode would ignore."""
     base = vars(add_fit_args(argparse.ArgumentParser()).parse_args([]))
     given = {k for k, v in vars(args).items() if k in base and v != base[k] and k != "config"}
-    bad = []
+    bad, extra = [], []
     if mode == "ps":
         bad += [k for k in _PS_IGNORED if k in given]
+        if args.optimizer in ("lars", "lamb"):
+            # the master applies the averaged gradient with its own fused sgd / adam / adamw (parallel/ps.py)
+            extra.append(f"--optimizer {args.optimizer}")
     else:
         bad += [k for k in _COLLECTIVE_IGNORED if k in given]
         if args.comm_type in ("Async",) and "comm_type" in given:
@@ -145,8 +155,8 @@ def check_mode_flags(args, mode: str, world: int):
             bad.append("straggler_mode")
         if mode == "single" and "opt_overlap" in given:
             bad.append("opt_overlap")
-    if bad:
-        flags = ", ".join("--" + k.replace("_", "-") for k in sorted(set(bad)))
+    if bad or extra:
+        flags = ", ".join(["--" + k.replace("_", "-") for k in sorted(set(bad))] + extra)
         raise SystemExit(f"--mode {mode} (world size {world}) does not use {flags}: remove them or pick the mode "
                          f"that implements them")
 
@@ -164,7 +174,7 @@ def main(argv=None):
     from .data.datasets import DataLoader, dataset_from_args
     from .models import build_model
     from .ops import functional as OF
-    from .optim import SGD, Adam, AdamW, flatten_module
+    from .optim import LAMB, LARS, SGD, Adam, AdamW, flatten_module
     from .parallel import runtime
     from .parallel.ddp import DistributedDataParallel
     from .trainer import Trainer
@@ -250,6 +260,11 @@ def main(argv=None):
         opt = SGD(params, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
     elif args.optimizer == "adam":
         opt = Adam(params, lr=args.lr, weight_decay=args.weight_decay)
+    elif args.optimizer == "lars":
+        opt = LARS(params, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay,
+                   trust_coef=args.trust_coef)
+    elif args.optimizer == "lamb":
+        opt = LAMB(params, lr=args.lr, weight_decay=args.weight_decay)
     else:
         opt = AdamW(params, lr=args.lr, weight_decay=args.weight_decay)
     if isinstance(net, DistributedDataParallel):

@@ -117,6 +117,11 @@ _SIGS = {
     "pdnn_sumsq_f32": [P, L, P, P],
     "pdnn_sumsq_partials": [P, L, P, I, P],          # returns the number of partials, or -hipError
     "pdnn_clip_coef": [P, I, F, F, P, P, P],
+    "pdnn_lw_chunk": [],
+    "pdnn_lw_norm_partials": [P, P, P, P, P, P, I, I, P, I, F, F, F, F, F, F, F, P, F, P, P],
+    "pdnn_lw_ratio": [P, P, I, I, I, F, F, I, P, F, P, P],
+    "pdnn_lars_apply": [P, P, P, P, P, P, I, I, P, F, F, F, I, I, P, F, P, P],
+    "pdnn_lamb_apply": [P, P, P, P, P, P, I, I, P, F, F, F, F, P, P],
     "pdnn_act_fwd": [P, P, L, I, P],
     "pdnn_act_bwd": [P, P, P, L, I, P],
     "pdnn_add": [P, P, P, L, F, F, P],

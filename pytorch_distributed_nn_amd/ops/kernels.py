@@ -1163,6 +1163,143 @@ def clip_coef(ws, nparts, max_norm, out, gscale=1.0, dev_scale=None):
     return out
 
 
+# Layer-wise optimizers (optim_layerwise.hip): LARS / LAMB over the SEGMENTS (one per parameter) of a flat range.
+# The kernels trust two device tables; LwTables builds them on the host, checks them and uploads them once.
+LW_CHUNK = 16384           # elements per chunk = per block (LW_CHUNK in optim_layerwise.hip)
+_LW_SEG = [("off", "<i8"), ("numel", "<i8"), ("wd", "<f4"), ("adapt", "<i4"), ("chunk0", "<i4"), ("nchunks", "<i4")]
+_LW_CHK = [("start", "<i8"), ("seg", "<i4"), ("len", "<i4")]
+
+
+def lw_chunks(segments):
+    """The chunk table rows ``(start, seg, len)`` of ``segments`` = [(offset, numel), ...]: every segment cut into
+    chunks of at most LW_CHUNK elements, in segment order."""
+    return [(off + a, si, min(LW_CHUNK, n - a)) for si, (off, n) in enumerate(segments)
+            for a in range(0, n, LW_CHUNK)]
+
+
+class LwTables:
+    """The segment and chunk tables of one flat range of ``extent`` elements, checked and uploaded to ``device``.
+
+    ``segments``: [(offset, numel, weight_decay, adapt)] in range order.  ``chunks`` (default: :func:`lw_chunks`)
+    is [(start, seg, len)].  Raises ``ValueError`` unless the segments are non-empty, ordered, non-overlapping and
+    inside [0, extent), and the chunks tile their segments exactly, in order, none longer than LW_CHUNK: the
+    kernels index memory with these numbers and check nothing."""
+
+    def __init__(self, segments, extent, device, chunks=None):
+        import numpy as np
+        segments = [(int(o), int(n), float(wd), int(bool(ad))) for o, n, wd, ad in segments]
+        _chk(len(segments) >= 1, "LwTables: no segments")
+        end = 0
+        for i, (o, n, wd, ad) in enumerate(segments):
+            _chk(n >= 1, f"LwTables: segment {i} is empty (numel {n})")
+            _chk(o >= end, f"LwTables: segment {i} at {o} overlaps or precedes the end {end} of segment {i - 1}")
+            _chk(wd == wd and abs(wd) != float("inf"), f"LwTables: segment {i} weight decay {wd}")
+            end = o + n
+        _chk(end <= int(extent), f"LwTables: segment {len(segments) - 1} ends at {end}, past the range ({extent})")
+        if chunks is None:
+            chunks = lw_chunks([(o, n) for o, n, _, _ in segments])
+        chunks = [(int(a), int(s), int(l)) for a, s, l in chunks]
+        _chk(len(chunks) < 2 ** 31, "LwTables: too many chunks")
+        seg = np.zeros(len(segments), dtype=_LW_SEG)
+        chk = np.zeros(len(chunks), dtype=_LW_CHK)
+        ci = 0
+        for si, (o, n, wd, ad) in enumerate(segments):
+            c0, pos = ci, o
+            while ci < len(chunks) and chunks[ci][1] == si:
+                a, _, l = chunks[ci]
+                _chk(a == pos and 1 <= l <= LW_CHUNK and a + l <= o + n,
+                     f"LwTables: chunk {ci} [{a}, {a + l}) does not continue segment {si} [{o}, {o + n}) at {pos}")
+                pos = a + l
+                ci += 1
+            _chk(pos == o + n, f"LwTables: the chunks of segment {si} cover [{o}, {pos}) of [{o}, {o + n})")
+            seg[si] = (o, n, wd, ad, c0, ci - c0)
+        _chk(ci == len(chunks), f"LwTables: chunk {ci} names segment {chunks[ci][1] if ci < len(chunks) else '?'} "
+                                "out of order or out of range")
+        for i, c in enumerate(chunks):
+            chk[i] = c
+        self.nseg, self.nchunk, self.extent = len(segments), len(chunks), int(extent)
+        self.segments, self.chunks = segments, chunks
+        self.seg = torch.from_numpy(seg.view(np.uint8)).to(device)
+        self.chk = torch.from_numpy(chk.view(np.uint8)).to(device)
+
+    def workspace(self):
+        """(partials[2 nchunk], out[3 nseg]): the norm pass's workspace and the ratio pass's result."""
+        dev = self.seg.device
+        return torch.zeros(2 * self.nchunk, dtype=F32, device=dev), torch.zeros(3 * self.nseg, dtype=F32, device=dev)
+
+
+def _lw_vec(t, n, name, dtype=F32, optional=False):
+    if t is None and optional:
+        return
+    _chk(t is not None and t.dtype == dtype and t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.numel() >= n,
+         f"{name}: expected a contiguous CUDA {dtype} vector of at least {n}")
+
+
+def _lw_scalar(t, name):
+    if t is not None:
+        _chk(t.dtype == F32 and t.is_cuda and t.numel() >= 1, f"{name} must be a CUDA fp32 scalar")
+
+
+def _lw_tab(tab, name):
+    _chk(isinstance(tab, LwTables) and tab.seg.is_cuda, f"{name}: tables must be LwTables on a CUDA device")
+
+
+def lw_norm_partials(p, g, tab, partials, m=None, v=None, b1=0.9, b2=0.999, eps=1e-6, bc1=1.0, bc2=1.0,
+                     gscale_dev=None, gscale=1.0, hyper=None):
+    """One block per chunk of ``tab``.  Without ``m``/``v`` (LARS): ``partials[2c], partials[2c + 1]`` = the chunk's
+    sums of w^2 and g^2.  With them (LAMB): the moment update of ``m`` and ``v`` from ``gscale * g``, then the sums
+    of w^2 and u^2, u = (m / bc1) / (sqrt(v / bc2) + eps) + wd_seg w.  ``p`` is only read."""
+    _lw_tab(tab, "lw_norm_partials")
+    lamb = m is not None or v is not None
+    for t, nm in ((p, "p"), (g, "g")) + (((m, "m"), (v, "v")) if lamb else ()):
+        _lw_vec(t, tab.extent, f"lw_norm_partials: {nm}")
+    _lw_vec(partials, 2 * tab.nchunk, "lw_norm_partials: workspace")
+    _lw_scalar(gscale_dev, "lw_norm_partials: gscale_dev")
+    call("pdnn_lw_norm_partials", ptr(p), ptr(g), ptr(m), ptr(v), ptr(tab.seg), ptr(tab.chk), tab.nseg, tab.nchunk,
+         ptr(partials), int(lamb), float(b1), float(b2), 1.0 - float(b1), 1.0 - float(b2), float(eps), float(bc1), float(bc2), ptr(gscale_dev),
+         float(gscale), ptr(hyper), stream())
+
+
+def lw_ratio(partials, tab, out, lamb, trust_coef=1e-3, eps=1e-8, clamp=False, gscale_dev=None, gscale=1.0):
+    """One block per segment: ``out[0:nseg]`` trust ratios, ``out[nseg:2 nseg]`` ||w||, ``out[2 nseg:3 nseg]`` the
+    other norm (LARS: |gscale| ||g||; LAMB: ||u||), from the chunk partials, added in table order in double."""
+    _lw_tab(tab, "lw_ratio")
+    _lw_vec(partials, 2 * tab.nchunk, "lw_ratio: workspace")
+    _lw_vec(out, 3 * tab.nseg, "lw_ratio: out")
+    _lw_scalar(gscale_dev, "lw_ratio: gscale_dev")
+    call("pdnn_lw_ratio", ptr(partials), ptr(tab.seg), tab.nseg, tab.nchunk, int(lamb), float(trust_coef), float(eps),
+         int(clamp), ptr(gscale_dev), float(gscale), ptr(out), stream())
+    return out
+
+
+def lars_apply(p, g, buf, shadow, tab, ratio, lr, momentum, dampening, nesterov, gscale_dev=None, gscale=1.0,
+               first=False, hyper=None):
+    """p -= lr * momentum-recurrence(ratio[seg] * (gscale * g + wd_seg * p)) over the segments of ``tab``; refreshes
+    ``shadow``.  ``hyper`` = [lr] overrides ``lr`` (graph replay)."""
+    _lw_tab(tab, "lars_apply")
+    _lw_vec(p, tab.extent, "lars_apply: p")
+    _lw_vec(g, tab.extent, "lars_apply: g")
+    _lw_vec(buf, tab.extent, "lars_apply: momentum buffer", optional=momentum == 0)
+    _lw_vec(shadow, tab.extent, "lars_apply: shadow", dtype=BF16, optional=True)
+    _lw_vec(ratio, tab.nseg, "lars_apply: ratio")
+    _lw_scalar(gscale_dev, "lars_apply: gscale_dev")
+    call("pdnn_lars_apply", ptr(p), ptr(g), ptr(buf), ptr(shadow), ptr(tab.seg), ptr(tab.chk), tab.nseg, tab.nchunk,
+         ptr(ratio), float(lr), float(momentum), float(dampening), int(nesterov), int(first), ptr(gscale_dev),
+         float(gscale), ptr(hyper), stream())
+
+
+def lamb_apply(p, m, v, shadow, tab, ratio, lr, eps, bc1, bc2, hyper=None):
+    """p -= lr * ratio[seg] * u over the segments of ``tab``, u recomputed from the stored moments; refreshes
+    ``shadow``.  ``hyper`` = [lr, 1-b1^t, 1-b2^t] overrides lr/bc1/bc2 (graph replay)."""
+    _lw_tab(tab, "lamb_apply")
+    for t, nm in ((p, "p"), (m, "m"), (v, "v")):
+        _lw_vec(t, tab.extent, f"lamb_apply: {nm}")
+    _lw_vec(shadow, tab.extent, "lamb_apply: shadow", dtype=BF16, optional=True)
+    _lw_vec(ratio, tab.nseg, "lamb_apply: ratio")
+    call("pdnn_lamb_apply", ptr(p), ptr(m), ptr(v), ptr(shadow), ptr(tab.seg), ptr(tab.chk), tab.nseg, tab.nchunk,
+         ptr(ratio), float(lr), float(eps), float(bc1), float(bc2), ptr(hyper), stream())
+
+
 # ----------------------------------------------------------------------------------- transformer
 def gemm_batched(a, lda, sa, amode, b, ldb, sb, bmode, c, ldc, sc, M, N, K, nb, alpha=1.0, res=None, causal=0):
     """Strided batched GEMM over nb = (nb1, nb2) batches: C = alpha * A . B (+res).

@@ -1,4 +1,5 @@
-"""Fused flat-buffer optimizers: SGD (momentum / dampening / weight decay / Nesterov) and Adam / AdamW.
+"""Fused flat-buffer optimizers: SGD (momentum / dampening / weight decay / Nesterov), Adam / AdamW, and the
+layer-wise LARS / LAMB (SGD / Adam under a per-tensor trust ratio, ``optim_layerwise.hip``).
 
 torch.optim-compatible API (``param_groups``, ``zero_grad``, ``state_dict``/``load_state_dict``,
 ``step(closure)``), semantics identical to ``torch.optim.SGD`` / ``Adam`` / ``AdamW``.
@@ -403,4 +404,247 @@ class AdamW(Adam):
         super().__init__(params, lr, betas, eps, weight_decay)
 
 
-__all__ = ["SGD", "Adam", "AdamW", "FlatParams"]
+# ------------------------------------------------------------------------------------ layer-wise: LARS / LAMB
+def _exclude_1d(p):
+    """The default ``exclude`` of LARS / LAMB: biases and normalisation gains (every parameter of at most 1-D)."""
+    return p.ndim <= 1
+
+
+class _LayerwiseBase(_FusedBase):
+    """SGD / Adam under a per-tensor trust ratio.  A param group on a contiguous GPU arena range is three launches
+    (optim_layerwise.hip): per-chunk norm partials, per-segment ratios, per-chunk update + bf16 shadow.  The
+    kernels know where each parameter begins and ends (segment / chunk tables, derived data cached per group like
+    ``_hyper``), so the arena's alignment padding is neither read into a norm nor written.  Loose tensors and CPU
+    arenas run the same formulas per parameter in torch ops.
+
+    ``exclude(p)`` -> True leaves a parameter out of weight decay and out of the scaling (ratio 1); ``None`` adapts
+    and decays everything.  ``trust_ratios(gi)`` / ``param_norms(gi)`` / ``update_norms(gi)`` return the last
+    step's per-parameter values of group ``gi``, in group order, as a device vector (no sync)."""
+    _LAMB = False
+
+    def __init__(self, params, defaults, exclude):
+        super().__init__(params, defaults)
+        self._exclude = exclude
+        self._lw = {}                  # gi -> tables, workspace, result of the fused path
+        self._lw_loose = {}            # gi -> [3, nparams] result of the torch-op path
+
+    def _excluded(self, p):
+        return self._exclude is not None and bool(self._exclude(p))
+
+    def _overlap_ok(self):             # a bucket holds parts of tensors: no per-bucket trust ratio
+        return None
+
+    # tables, workspace and result vector of group gi; built on first use and whenever the group's weight decay
+    # changes -- outside any graph capture (graph_mode() calls this, as it allocates _hyper)
+    def _lw_prepare(self, gi, group):
+        from ..ops import kernels as K
+        fp, (s, e) = self._group_flat(gi, group)
+        wd = float(group["weight_decay"])
+        lw = self._lw.get(gi)
+        if lw is not None and lw["wd"] == wd:
+            return lw
+        idx = [p._pdnn_flat_idx for p in group["params"]]
+        order = sorted(range(len(idx)), key=lambda j: idx[j])          # table (arena) order -> group position
+        segs = []
+        for j in order:
+            p = group["params"][j]
+            ex = self._excluded(p)
+            segs.append((fp.offsets[idx[j]] - s, p.numel(), 0.0 if ex else wd, not ex))
+        tab = K.LwTables(segs, e - s, fp.data.device)
+        ws, out = tab.workspace()
+        perm = None
+        if order != list(range(len(idx))):
+            inv = [0] * len(order)
+            for t, j in enumerate(order):
+                inv[j] = t
+            perm = torch.tensor(inv, dtype=torch.long, device=fp.data.device)
+        lw = self._lw[gi] = dict(wd=wd, tab=tab, ws=ws, out=out, perm=perm)
+        return lw
+
+    def graph_mode(self, on: bool = True):
+        if on:
+            for gi, group in enumerate(self.param_groups):
+                fp, _ = self._group_flat(gi, group)
+                if fp is not None and fp.data.is_cuda:
+                    self._lw_prepare(gi, group)
+        super().graph_mode(on)
+
+    def _lw_result(self, gi, row):
+        lw = self._lw.get(gi)
+        if lw is not None:
+            n = lw["tab"].nseg
+            v = lw["out"][row * n:(row + 1) * n]
+            return v if lw["perm"] is None else v.index_select(0, lw["perm"])
+        res = self._lw_loose.get(gi)
+        return None if res is None else res[row]
+
+    def trust_ratios(self, gi: int = 0):
+        """Device vector: the last step's trust ratio of every parameter of group ``gi`` (None before a step)."""
+        return self._lw_result(gi, 0)
+
+    def param_norms(self, gi: int = 0):
+        """Device vector: ||w|| of every parameter of group ``gi`` in front of the last step."""
+        return self._lw_result(gi, 1)
+
+    def update_norms(self, gi: int = 0):
+        """Device vector: the norm under the last step's ratios: the gradient's as the update saw it (LARS), or
+        that of u = m^ / (sqrt(v^) + eps) + wd w (LAMB)."""
+        return self._lw_result(gi, 2)
+
+    def _ratio(self, wn, un, r, adapt, clamp):
+        """The kernels' rule in torch ops: 1 unless adapted with both norms non-zero; a NaN norm gives NaN."""
+        if not adapt:
+            return torch.ones_like(wn)
+        if clamp:
+            r = torch.where(r > 1, torch.ones_like(r), r)
+        return torch.where((wn == 0) | (un == 0), torch.ones_like(wn), r)
+
+    def _scaled_grad(self, p, gsd):
+        g = p.grad
+        if self.grad_scale != 1.0:
+            g = g * self.grad_scale
+        if gsd is not None:
+            g = g * gsd.to(g.device).reshape(())
+        return g
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        gsd = self._clip_scale()
+        for gi, group in enumerate(self.param_groups):
+            fp, rng = self._group_flat(gi, group)
+            if fp is not None and fp.data.is_cuda:
+                self._step_fused(gi, group, fp, rng, gsd)
+                fp.generation += 1
+                continue
+            rows = [self._step_param(group, p, gsd) for p in group["params"] if p.grad is not None]
+            if rows:
+                self._lw_loose[gi] = torch.stack([torch.stack(r) for r in rows], dim=1)
+        return loss
+
+
+class LARS(_LayerwiseBase):
+    """Layer-wise adaptive rate scaling (You, Gitman, Ginsburg 2017) on SGD's momentum recurrence:
+
+        r = trust_coef * ||w|| / (||g|| + wd * ||w|| + eps)        (g as the update sees it: scaled, clipped)
+        d = r * (g + wd * w);   then SGD's momentum / dampening / Nesterov on d;   w -= lr * (...)
+
+    per parameter; r = 1 for an excluded parameter (which also gets no weight decay), when ||w|| = 0 or ||g|| = 0;
+    ``clamp`` caps r at 1 (LARC)."""
+
+    def __init__(self, params, lr, momentum=0.9, dampening=0.0, weight_decay=0.0, nesterov=False, trust_coef=1e-3,
+                 eps=1e-8, clamp=False, exclude=_exclude_1d):
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                      nesterov=nesterov, trust_coef=trust_coef, eps=eps, clamp=clamp), exclude)
+
+    def _check_graphable(self, gi):
+        if self.param_groups[gi]["momentum"] != 0 and "momentum_buffer" not in self.state.get(f"flat{gi}", {}):
+            raise RuntimeError("LARS graph mode: run one eager step before capture (momentum buffer init)")
+
+    def _step_fused(self, gi, group, fp, rng, gsd):
+        from ..ops import kernels as K
+        s, e = rng
+        lw = self._lw_prepare(gi, group)
+        st = self.state.setdefault(f"flat{gi}", {})
+        first = "momentum_buffer" not in st
+        if group["momentum"] != 0 and first:
+            st["momentum_buffer"] = torch.zeros(e - s, device=fp.data.device)
+        hyper = self._hyper_buf(gi, 1, fp.data.device) if self._graph else None
+        tab, n = lw["tab"], lw["tab"].nseg
+        p, g = fp.data[s:e], fp.grad[s:e]
+        K.lw_norm_partials(p, g, tab, lw["ws"], gscale_dev=gsd, gscale=self.grad_scale)
+        K.lw_ratio(lw["ws"], tab, lw["out"], False, group["trust_coef"], group["eps"], group["clamp"], gsd,
+                   self.grad_scale)
+        K.lars_apply(p, g, st.get("momentum_buffer"), fp.shadow[s:e] if fp.shadow is not None else None, tab,
+                     lw["out"][:n], group["lr"], group["momentum"], group["dampening"], group["nesterov"], gsd,
+                     self.grad_scale, first, hyper=hyper)
+
+    def _step_param(self, group, p, gsd):
+        lr, mom, damp, nest = group["lr"], group["momentum"], group["dampening"], group["nesterov"]
+        ex = self._excluded(p)
+        wd = 0.0 if ex else group["weight_decay"]
+        g = self._scaled_grad(p, gsd)
+        wn, un = torch.linalg.vector_norm(p), torch.linalg.vector_norm(g)
+        r = self._ratio(wn, un, group["trust_coef"] * wn / (un + wd * wn + group["eps"]), not ex, group["clamp"])
+        d = (g.add(p, alpha=wd) if wd != 0 else g) * r
+        if mom != 0:
+            st = self.state[p]
+            if "momentum_buffer" not in st:
+                st["momentum_buffer"] = d.clone().detach()
+            else:
+                st["momentum_buffer"].mul_(mom).add_(d, alpha=1 - damp)
+            b = st["momentum_buffer"]
+            d = d.add(b, alpha=mom) if nest else b
+        p.add_(d, alpha=-lr)
+        return r, wn, un
+
+
+class LAMB(_LayerwiseBase):
+    """Layer-wise adaptive moments (You et al. 2020): Adam's moments m, v of the gradient as the update sees it,
+
+        u = (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps) + wd * w;     r = ||w|| / ||u||;     w -= lr * r * u
+
+    per parameter; r = 1 for an excluded parameter (which also gets no weight decay), when ||w|| = 0 or ||u|| = 0;
+    ``clamp`` caps r at 1."""
+    _LAMB = True
+    _HYPER_LEN = 3
+    _hyper_values = Adam._hyper_values
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, clamp=False,
+                 exclude=_exclude_1d):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clamp=clamp), exclude)
+
+    def _step_fused(self, gi, group, fp, rng, gsd):
+        from ..ops import kernels as K
+        s, e = rng
+        lw = self._lw_prepare(gi, group)
+        st = self.state.setdefault(f"flat{gi}", {})
+        if "step" not in st:
+            st["step"] = 0
+            st["exp_avg"] = torch.zeros(e - s, device=fp.data.device)
+            st["exp_avg_sq"] = torch.zeros(e - s, device=fp.data.device)
+        hyper = None
+        if self._graph:                          # t advances in pre_replay(); the kernels read hyper[]
+            hyper = self._hyper_buf(gi, 3, fp.data.device)
+        else:
+            st["step"] += 1
+        t = max(st["step"], 1)
+        (b1, b2), eps = group["betas"], group["eps"]
+        bc1, bc2 = 1 - b1 ** t, 1 - b2 ** t
+        tab, n = lw["tab"], lw["tab"].nseg
+        p, m, v = fp.data[s:e], st["exp_avg"], st["exp_avg_sq"]
+        K.lw_norm_partials(p, fp.grad[s:e], tab, lw["ws"], m, v, b1, b2, eps, bc1, bc2, gsd, self.grad_scale,
+                           hyper=hyper)
+        K.lw_ratio(lw["ws"], tab, lw["out"], True, clamp=group["clamp"])
+        K.lamb_apply(p, m, v, fp.shadow[s:e] if fp.shadow is not None else None, tab, lw["out"][:n], group["lr"],
+                     eps, bc1, bc2, hyper=hyper)
+
+    def _step_param(self, group, p, gsd):
+        (b1, b2), eps = group["betas"], group["eps"]
+        ex = self._excluded(p)
+        wd = 0.0 if ex else group["weight_decay"]
+        g = self._scaled_grad(p, gsd)
+        st = self.state[p]
+        if "step" not in st:
+            st["step"] = 0
+            st["exp_avg"] = torch.zeros_like(p)
+            st["exp_avg_sq"] = torch.zeros_like(p)
+        st["step"] += 1
+        t = st["step"]
+        st["exp_avg"].lerp_(g, 1 - b1)
+        st["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1 - b2)
+        u = (st["exp_avg"] / (1 - b1 ** t)) / ((st["exp_avg_sq"].sqrt() / math.sqrt(1 - b2 ** t)).add_(eps))
+        if wd != 0:
+            u = u.add(p, alpha=wd)
+        wn, un = torch.linalg.vector_norm(p), torch.linalg.vector_norm(u)
+        r = self._ratio(wn, un, wn / un, not ex, group["clamp"])
+        p.sub_(u * (group["lr"] * r))
+        return r, wn, un
+
+
+__all__ = ["SGD", "Adam", "AdamW", "LARS", "LAMB", "FlatParams"]
