@@ -10,7 +10,9 @@ reference's behaviour; ddp when --comm-type AllReduce), --comm-type AllReduce, -
 --trust-coef ETA (lars; lars and lamb scale each tensor's step by a trust ratio ||w|| / ||update|| and leave 1-D
 parameters, biases and normalisation gains, out of the scaling and out of weight decay; not in PS mode, whose master
 applies its own fused SGD / Adam, and not with --opt-overlap's per-bucket update),
---grad-clip NORM (global L2 norm, fused into the optimizer step; 0 = off), --opt-overlap (DDP per-bucket updates),
+--grad-clip NORM (global L2 norm, fused into the optimizer step; 0 = off),
+--label-smoothing EPS and --z-loss Z (training loss only: the fused cross-entropy kernels mix the target with the
+uniform distribution and add Z * logsumexp^2; evaluation reports the plain cross-entropy), --opt-overlap (DDP per-bucket updates),
 --n-to-collect (backup workers), --interval-ms, --no-shortcircuit, --evaluator,
 --inject-straggler RANK:MS[,RANK:MS], --straggler-mode (k-of-n inside DDP), --checkpoint-dir, --resume,
 --trace FILE, --metrics FILE.
@@ -55,6 +57,11 @@ def add_fit_args(p: argparse.ArgumentParser):
     p.add_argument("--grad-clip", type=float, default=0.0, metavar="NORM",
                    help="clip the gradient to this global L2 norm before the update (0 = off); the fused optimizers "
                         "do it inside their step, one read of the flat gradient (optim/fused.py set_grad_clip)")
+    p.add_argument("--label-smoothing", type=float, default=0.0, metavar="EPS",
+                   help="training loss: target = (1 - EPS) onehot + EPS / classes, inside the fused cross-entropy "
+                        "kernels (0 = off; evaluation keeps the plain loss)")
+    p.add_argument("--z-loss", type=float, default=0.0, metavar="Z",
+                   help="training loss: + Z * logsumexp(logits)^2 per sample (PaLM's auxiliary loss; 0 = off)")
     p.add_argument("--opt-overlap", action="store_true",
                    help="DDP: apply each bucket's optimizer update right after its all-reduce, beside the rest of "
                         "the backward (DistributedDataParallel.overlap_optimizer); not with --grad-clip")
@@ -119,6 +126,10 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.grad_clip < 0:
         raise SystemExit("--grad-clip must be >= 0 (0 = off)")
+    if not 0.0 <= args.label_smoothing <= 1.0:
+        raise SystemExit("--label-smoothing must be in [0, 1] (0 = off)")
+    if not 0.0 <= args.z_loss < float("inf"):
+        raise SystemExit("--z-loss must be finite and >= 0 (0 = off)")
     if args.grad_clip and args.opt_overlap:
         raise SystemExit("--grad-clip cannot be combined with --opt-overlap: the overlapped optimizer updates each "
                          "bucket during the backward, before the gradient's global norm exists")
@@ -200,6 +211,13 @@ def main(argv=None):
         else:
             raise SystemExit(f"--dtype fp8: network {args.network} has no fp8 path (ResNet Bottlenecks, GPT-2)")
     xdt = torch.bfloat16 if (dev.type == "cuda" and args.dtype in ("bf16", "fp8")) else torch.float32
+    # the training loss; evaluation (evaluate below, Trainer.evaluate, evaluator.py) keeps the plain cross-entropy
+    train_loss = OF.cross_entropy
+    if args.label_smoothing or args.z_loss:
+        import functools
+        train_loss = functools.partial(OF.cross_entropy, label_smoothing=args.label_smoothing, z_loss=args.z_loss)
+        if hasattr(getattr(model, "config", None), "label_smoothing"):      # GPT-2 computes its loss itself
+            model.config.label_smoothing, model.config.z_loss = args.label_smoothing, args.z_loss
 
     def to_dev(batch):
         x, y = batch
@@ -240,7 +258,7 @@ def main(argv=None):
                 yt = torch.as_tensor(y).to(dev)
                 return float(OF.cross_entropy(out, yt)), float((out.argmax(1) != yt).float().mean())
 
-        out = run_ps(model, cfg, dev, loss_fn=OF.cross_entropy, batches=batches(), eval_fn=evaluate)
+        out = run_ps(model, cfg, dev, loss_fn=train_loss, batches=batches(), eval_fn=evaluate)
         if rank == 0:
             print(f"Master: finished {len(out)} steps; gradients used per step: {[r['count'] for r in out][-10:]}")
         runtime.destroy()
@@ -320,10 +338,10 @@ def main(argv=None):
     if args.lr_decay_factor != 1.0 and args.epochs_per_decay > 0:
         decay_steps = max(1, int(len(loader) * args.epochs_per_decay))
         lr_schedule = lambda step, lr0=args.lr, f=args.lr_decay_factor: lr0 * f ** (step // decay_steps)  # noqa: E731
-    tr = Trainer(net, opt, OF.cross_entropy, dev, rank, world, args.log_interval, args.metrics,
+    tr = Trainer(net, opt, train_loss, dev, rank, world, args.log_interval, args.metrics,
                  args.trace, args.checkpoint_dir, arch=args.network, printer=print if rank == 0 else (lambda *a: None),
                  graph=graph, checkpoint_interval=args.checkpoint_interval, watchdog=wd, lr_schedule=lr_schedule,
-                 grad_clip=args.grad_clip or None,
+                 grad_clip=args.grad_clip or None, eval_loss_fn=OF.cross_entropy,
                  compute_log=(os.path.join(args.out_dir, f"compute_times_rank{rank}.jsonl")
                               if args.compute_times else None))
     if args.resume:

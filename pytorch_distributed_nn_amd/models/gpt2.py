@@ -37,6 +37,9 @@ class GPT2Config:
     n_embd: int = 768
     eps: float = 1e-5
     fp8: bool = False          # block linears' forward GEMMs in fp8 (e4m3, delayed scaling); bwd bf16
+    # training loss only (grad mode on); an evaluation forward returns the plain cross-entropy
+    label_smoothing: float = 0.0   # eps: target = (1 - eps) onehot + eps / vocab_size
+    z_loss: float = 0.0            # z: + z * logsumexp^2 per token (PaLM)
 
 
 CONFIGS = {
@@ -193,8 +196,10 @@ class GPT2(nn.Module):
         if targets is None:
             xf = TX.layer_norm(x, tr.ln_f.weight, tr.ln_f.bias, c.eps)
             return OF.linear(xf, wte).view(B, T, -1)
+        train = torch.is_grad_enabled()
         return TX.LMHeadLossFn.apply(x, targets.reshape(-1).long().contiguous(), c.eps, wte_k, tr.ln_f.weight,
-                                     tr.ln_f.bias, wte, hd, ddp is not None, torch.is_grad_enabled())
+                                     tr.ln_f.bias, wte, hd, ddp is not None, train,
+                                     c.label_smoothing if train else 0.0, c.z_loss if train else 0.0)
 
     def _forward_reference(self, idx, targets=None):
         B, T = idx.shape
@@ -210,7 +215,15 @@ class GPT2(nn.Module):
         logits = self.lm_head(tr.ln_f(x))
         if targets is None:
             return logits
-        return F.cross_entropy(logits.float().view(-1, logits.shape[-1]), targets.reshape(-1))
+        lg, t = logits.float().view(-1, logits.shape[-1]), targets.reshape(-1)
+        c = self.config
+        if not torch.is_grad_enabled() or not (c.label_smoothing or c.z_loss):
+            return F.cross_entropy(lg, t)
+        loss = F.cross_entropy(lg, t, label_smoothing=c.label_smoothing)
+        if c.z_loss:
+            ok = t != -100
+            loss = loss + c.z_loss * (torch.logsumexp(lg, -1) ** 2 * ok).sum() / ok.sum().clamp_min(1)
+        return loss
 
 
 class _RowTailEmbedding(torch.autograd.Function):

@@ -391,10 +391,10 @@ def avg_pool2d_nhwc(x, k):
 # ------------------------------------------------------------------------------------------------
 class _XEnt(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, target, ignore_index, reduction):
-        loss, lse, acc = K.xent_fwd(logits, target, ignore_index)
+    def forward(ctx, logits, target, ignore_index, reduction, label_smoothing=0.0, z_loss=0.0):
+        loss, lse, acc = K.xent_fwd(logits, target, ignore_index, label_smoothing, z_loss)
         ctx.save_for_backward(logits, target, lse, acc)
-        ctx.conf = (ignore_index, reduction)
+        ctx.conf = (ignore_index, reduction, label_smoothing, z_loss)
         if reduction == "sum":
             return acc[0].clone()
         if reduction == "none":
@@ -404,27 +404,56 @@ class _XEnt(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         logits, target, lse, acc = ctx.saved_tensors
-        ignore_index, reduction = ctx.conf
+        ignore_index, reduction, eps, z = ctx.conf
         if reduction == "none":
             # per-row scale: fold into labels-independent path (rare; small tensors)
             p = torch.softmax(logits.float(), -1)
-            p[torch.arange(p.shape[0], device=p.device), target.clamp_min(0)] -= 1
-            p = p * (target != ignore_index).unsqueeze(1) * g.unsqueeze(1)
-            return p.to(logits.dtype), None, None, None
+            V = p.shape[1]
+            ok = (target != ignore_index) & (target >= 0) & (target < V)
+            if eps or z:        # (1 + 2 z lse) softmax - (1 - eps) onehot - eps / V
+                p = p * (1.0 + 2.0 * z * lse).unsqueeze(1) - eps / V
+            p[torch.arange(p.shape[0], device=p.device), target.clamp(0, V - 1)] -= 1.0 - eps
+            p = p * ok.unsqueeze(1) * g.unsqueeze(1)
+            return p.to(logits.dtype), None, None, None, None, None
         gs = g.reshape(1)
         if gs.dtype != torch.float32:
             gs = gs.float()
-        d = K.xent_bwd(logits, target, lse, gs, 1.0, ignore_index, count=acc[1:2] if reduction == "mean" else None)
-        return d, None, None, None
+        d = K.xent_bwd(logits, target, lse, gs, 1.0, ignore_index, count=acc[1:2] if reduction == "mean" else None,
+                       label_smoothing=eps, z_loss=z)
+        return d, None, None, None, None, None
 
 
-def cross_entropy(logits, target, ignore_index=-100, reduction="mean"):
+def _check_ls(label_smoothing, z_loss):
+    eps, z = float(label_smoothing), float(z_loss)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"cross_entropy: label_smoothing must be in [0, 1], got {label_smoothing!r}")
+    if not 0.0 <= z < float("inf"):
+        raise ValueError(f"cross_entropy: z_loss must be finite and >= 0, got {z_loss!r}")
+    return eps, z
+
+
+def cross_entropy(logits, target, ignore_index=-100, reduction="mean", label_smoothing=0.0, z_loss=0.0):
+    """Softmax cross-entropy over the last dimension.  ``label_smoothing`` eps mixes the target with the uniform
+    distribution over the V classes (``F.cross_entropy(label_smoothing=)``), ``z_loss`` z adds z * logsumexp^2 on
+    every row with a valid label (the PaLM auxiliary loss); both are part of the fused kernels' single pass."""
+    eps, z = _check_ls(label_smoothing, z_loss)
     if not logits.is_cuda:
-        return F.cross_entropy(logits.float(), target, ignore_index=ignore_index, reduction=reduction)
+        lg = logits.float()
+        loss = F.cross_entropy(lg, target, ignore_index=ignore_index, reduction=reduction, label_smoothing=eps)
+        if z:
+            lg2, t = lg.reshape(-1, lg.shape[-1]), target.reshape(-1)
+            zl = z * torch.logsumexp(lg2, -1) ** 2 * (t != ignore_index)
+            if reduction == "none":
+                loss = loss + zl.reshape(loss.shape)
+            elif reduction == "sum":
+                loss = loss + zl.sum()
+            else:
+                loss = loss + zl.sum() / (t != ignore_index).sum().clamp_min(1)
+        return loss
     lg = logits.reshape(-1, logits.shape[-1])
     if lg.dtype not in (BF16, torch.float32):
         lg = lg.float()
-    return _XEnt.apply(lg.contiguous(), target.reshape(-1).long().contiguous(), ignore_index, reduction)
+    return _XEnt.apply(lg.contiguous(), target.reshape(-1).long().contiguous(), ignore_index, reduction, eps, z)
 
 
 # ------------------------------------------------------------------------------------------------

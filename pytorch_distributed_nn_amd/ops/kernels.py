@@ -976,8 +976,19 @@ def _xent_rows(labels, R, lse=None):
                          and lse.is_cuda), "xent: lse must be contiguous fp32 [rows] on the device")
 
 
-def xent_fwd(logits, labels, ignore_index=-100):
+def _xent_ls(label_smoothing, z_loss):
+    """The label-smoothing / z-loss pair of the xent wrappers as floats; (0, 0) selects the plain entry points."""
+    eps, z = float(label_smoothing), float(z_loss)
+    _chk(0.0 <= eps <= 1.0, "xent: label_smoothing must be in [0, 1]")
+    _chk(0.0 <= z < float("inf"), "xent: z_loss must be finite and >= 0")
+    return eps, z
+
+
+def xent_fwd(logits, labels, ignore_index=-100, label_smoothing=0.0, z_loss=0.0):
+    """Per-row loss and lse, acc = [loss sum, valid-label count].  With label_smoothing eps / z_loss z the row loss
+    is (1 - eps) (lse - x[y]) + eps (lse - mean x) + z lse^2 (the pdnn_xent_ls_* entry points)."""
     R, V = logits.shape
+    eps, z = _xent_ls(label_smoothing, z_loss)
     _chk(logits.stride(1) == 1, "xent: row-major logits")
     dt = 1 if logits.dtype == BF16 else 0
     _chk(logits.dtype in (BF16, F32), "xent: bf16/fp32 logits")
@@ -985,8 +996,12 @@ def xent_fwd(logits, labels, ignore_index=-100):
     loss = torch.empty(R, device=logits.device, dtype=F32)
     lse = torch.empty(R, device=logits.device, dtype=F32)
     acc = torch.empty(2, device=logits.device, dtype=F32)          # [loss sum, valid-label count], set by the call
-    call("pdnn_xent_fwd", ptr(logits), logits.stride(0), R, V, ptr(labels), int(ignore_index), ptr(loss), ptr(lse),
-         ptr(acc), ptr(acc[1:]), dt, stream())
+    if eps == 0.0 and z == 0.0:
+        call("pdnn_xent_fwd", ptr(logits), logits.stride(0), R, V, ptr(labels), int(ignore_index), ptr(loss),
+             ptr(lse), ptr(acc), ptr(acc[1:]), dt, stream())
+    else:
+        call("pdnn_xent_ls_fwd", ptr(logits), logits.stride(0), R, V, ptr(labels), int(ignore_index), eps, z,
+             ptr(loss), ptr(lse), ptr(acc), ptr(acc[1:]), dt, stream())
     return loss, lse, acc
 
 
@@ -997,11 +1012,13 @@ def xent_fwd_grad_ok(logits):
             and V <= 51200 and logits.data_ptr() % 16 == 0)
 
 
-def xent_fwd_grad(logits, labels, ignore_index=-100, out=None):
+def xent_fwd_grad(logits, labels, ignore_index=-100, out=None, label_smoothing=0.0, z_loss=0.0):
     """Training forward of the cross-entropy that also writes d logits = softmax - onehot, UNSCALED (the caller
     applies grad_out / count downstream), into ``out`` (default: in place over ``logits``).  One read and one
     write of the logits instead of the forward's read plus the backward's read and write.  Returns
-    (loss per row, lse, acc = [loss sum, valid-label count], dlogits)."""
+    (loss per row, lse, acc = [loss sum, valid-label count], dlogits).  With label_smoothing eps / z_loss z the
+    gradient is (1 + 2 z lse) softmax - (1 - eps) onehot - eps / V, still unscaled."""
+    eps, z = _xent_ls(label_smoothing, z_loss)
     _chk(xent_fwd_grad_ok(logits), "xent_fwd_grad: bf16 row-major logits, V % 8 == 0, V <= 51200")
     R, V = logits.shape
     d = logits if out is None else out
@@ -1011,15 +1028,21 @@ def xent_fwd_grad(logits, labels, ignore_index=-100, out=None):
     loss = torch.empty(R, device=logits.device, dtype=F32)
     lse = torch.empty(R, device=logits.device, dtype=F32)
     acc = torch.empty(2, device=logits.device, dtype=F32)
-    call("pdnn_xent_fwd_grad", ptr(logits), logits.stride(0), R, V, ptr(labels), int(ignore_index), ptr(loss),
-         ptr(lse), ptr(acc), ptr(acc[1:]), ptr(d), d.stride(0), stream())
+    if eps == 0.0 and z == 0.0:
+        call("pdnn_xent_fwd_grad", ptr(logits), logits.stride(0), R, V, ptr(labels), int(ignore_index), ptr(loss),
+             ptr(lse), ptr(acc), ptr(acc[1:]), ptr(d), d.stride(0), stream())
+    else:
+        call("pdnn_xent_ls_fwd_grad", ptr(logits), logits.stride(0), R, V, ptr(labels), int(ignore_index), eps, z,
+             ptr(loss), ptr(lse), ptr(acc), ptr(acc[1:]), ptr(d), d.stride(0), stream())
     return loss, lse, acc, d
 
 
-def xent_bwd(logits, labels, lse, gscale_dev, denom, ignore_index=-100, count=None):
+def xent_bwd(logits, labels, lse, gscale_dev, denom, ignore_index=-100, count=None, label_smoothing=0.0, z_loss=0.0):
     """d logits = softmax - onehot, times gscale_dev[0] / denom, or gscale_dev[0] / max(count[0], 1) with
-    ``count`` (fp32 device scalar: xent_fwd's count of non-ignored rows, the mean reduction)."""
+    ``count`` (fp32 device scalar: xent_fwd's count of non-ignored rows, the mean reduction).  With label_smoothing
+    eps / z_loss z the unscaled gradient is (1 + 2 z lse) softmax - (1 - eps) onehot - eps / V."""
     R, V = logits.shape
+    eps, z = _xent_ls(label_smoothing, z_loss)
     _chk(logits.stride(1) == 1 and logits.dtype in (BF16, F32), "xent_bwd: row-major bf16/fp32 logits")
     _xent_rows(labels, R, lse)
     d = torch.empty_like(logits)
@@ -1027,8 +1050,12 @@ def xent_bwd(logits, labels, lse, gscale_dev, denom, ignore_index=-100, count=No
     _chk(gscale_dev.dtype == F32 and gscale_dev.is_cuda, "xent_bwd: fp32 device gscale")
     _chk(count is None or (count.dtype == F32 and count.is_cuda and count.numel() >= 1),
          "xent_bwd: fp32 device count")
-    call("pdnn_xent_bwd", ptr(logits), logits.stride(0), R, V, ptr(labels), int(ignore_index), ptr(lse),
-         ptr(gscale_dev), float(denom), ptr(count), ptr(d), d.stride(0), dt, stream())
+    if eps == 0.0 and z == 0.0:
+        call("pdnn_xent_bwd", ptr(logits), logits.stride(0), R, V, ptr(labels), int(ignore_index), ptr(lse),
+             ptr(gscale_dev), float(denom), ptr(count), ptr(d), d.stride(0), dt, stream())
+    else:
+        call("pdnn_xent_ls_bwd", ptr(logits), logits.stride(0), R, V, ptr(labels), int(ignore_index), eps, z,
+             ptr(lse), ptr(gscale_dev), float(denom), ptr(count), ptr(d), d.stride(0), dt, stream())
     return d
 
 

@@ -345,10 +345,13 @@ class GPT2BlockFn(torch.autograd.Function):
 # final LayerNorm + tied LM head + cross-entropy
 # ------------------------------------------------------------------------------------------------
 class LMHeadLossFn(torch.autograd.Function):
-    """loss = mean CE(LN_f(x) . Wte^T, targets); logits bf16 [B*T][V] live only inside this op."""
+    """loss = mean CE(LN_f(x) . Wte^T, targets); logits bf16 [B*T][V] live only inside this op.  ``label_smoothing``
+    and ``z_loss`` select the smoothed / z-regularised loss of the same kernels (ops/kernels.py xent_fwd)."""
 
     @staticmethod
-    def forward(ctx, x, targets, eps, wte_k, lnw, lnb, wte, head_direct=False, split=False, training=False):
+    def forward(ctx, x, targets, eps, wte_k, lnw, lnb, wte, head_direct=False, split=False, training=False,
+                label_smoothing=0.0, z_loss=0.0):
+        ctx.ls = (label_smoothing, z_loss)
         ctx.head_direct = head_direct
         ctx.split = split                   # split tied embedding: the head announces wte itself
         xf, m, r = K.layernorm_fwd(x, lnw, lnb, eps)
@@ -358,9 +361,9 @@ class LMHeadLossFn(torch.autograd.Function):
         # scales the head's 8192 x 768 products by grad_out / count instead of the logits gradient
         ctx.fused = training and _tuning.get("xent_fused") and logits.is_cuda and K.xent_fwd_grad_ok(logits)
         if ctx.fused:
-            _, lse, acc, _ = K.xent_fwd_grad(logits, targets)
+            _, lse, acc, _ = K.xent_fwd_grad(logits, targets, label_smoothing=label_smoothing, z_loss=z_loss)
         else:
-            _, lse, acc = K.xent_fwd(logits, targets)
+            _, lse, acc = K.xent_fwd(logits, targets, label_smoothing=label_smoothing, z_loss=z_loss)
         ctx.save_for_backward(x, xf, m, r, logits, targets, lse, acc, lnw, wte_k)
         ctx.eps = eps
         ctx.params = (lnw, lnb)
@@ -373,7 +376,7 @@ class LMHeadLossFn(torch.autograd.Function):
         gs = g.reshape(1)
         if gs.dtype != torch.float32:
             gs = gs.float()
-        if ctx.fused:           # logits hold softmax - onehot: scale the products instead (device scalar, no sync)
+        if ctx.fused:           # logits hold the unscaled gradient: scale the products instead (device scalar, no sync)
             dlogits = logits
             sc = gs / acc[1:2].clamp_min(1.0)
             dxf = BL.linear_dgrad(dlogits, wte_k, p=ctx.wte)
@@ -381,7 +384,8 @@ class LMHeadLossFn(torch.autograd.Function):
             xf = xf.clone()
             xf.mul_(sc)
         else:
-            dlogits = K.xent_bwd(logits, targets, lse, gs, 1.0, count=acc[1:2])
+            dlogits = K.xent_bwd(logits, targets, lse, gs, 1.0, count=acc[1:2], label_smoothing=ctx.ls[0],
+                                 z_loss=ctx.ls[1])
             dxf = BL.linear_dgrad(dlogits, wte_k, p=ctx.wte)
         tte = direct_grad(ctx.wte) if ctx.head_direct else None
         if tte is not None:     # tied weight: the embedding backward adds its part and announces it
@@ -396,4 +400,4 @@ class LMHeadLossFn(torch.autograd.Function):
         ctx.params = None
         ctx.wte = None
         sink.done()
-        return dx, None, None, None, dlnw, dlnb, dwte, None, None, None
+        return dx, None, None, None, dlnw, dlnb, dwte, None, None, None, None, None

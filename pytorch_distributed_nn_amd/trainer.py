@@ -25,10 +25,12 @@ class Trainer:
     def __init__(self, model, optimizer, loss_fn=None, device=None, rank=0, world=1, log_interval=10,
                  metrics_path=None, trace_path=None, checkpoint_dir=None, arch="", timing=True, printer=print,
                  lr_schedule=None, grad_clip=None, graph=False, graph_warmup=2, checkpoint_interval=0,
-                 watchdog=None, compute_log=None):
+                 watchdog=None, compute_log=None, eval_loss_fn=None):
         self.model = model
         self.opt = optimizer
         self.loss_fn = loss_fn or OF.cross_entropy
+        # evaluate()'s loss: a smoothed / z-regularised training loss is not what validation reports
+        self.eval_loss_fn = eval_loss_fn or self.loss_fn
         self.device = device or torch.device("cpu")
         self.rank, self.world = rank, world
         self.log_interval = log_interval
@@ -251,7 +253,7 @@ class Trainer:
             x, y = next(it)
             x, y = x.to(self.device), y.to(self.device)
             out = self.model(x)
-            tot_loss += float(self.loss_fn(out, y)) * x.shape[0]
+            tot_loss += float(self.eval_loss_fn(out, y)) * x.shape[0]
             k5 = min(5, out.shape[1])
             p1, p5 = accuracy(out, y, (1, k5))
             p1s += float(p1) * x.shape[0]
