@@ -1157,16 +1157,18 @@ CLIP_PARTS = 512
 CLIP_WS = CLIP_RANGES * CLIP_PARTS
 
 
-def _clip_f32(t, n, name):
-    _chk(t is not None and t.dtype == F32 and t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.numel() >= n,
-         f"{name}: expected a contiguous CUDA fp32 vector of at least {n}")
+def _vec(t, n, name, dtype=F32, optional=False):
+    if t is None and optional:
+        return
+    _chk(t is not None and t.dtype == dtype and t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.numel() >= n,
+         f"{name}: expected a contiguous CUDA {dtype} vector of at least {n}")
 
 
 def sumsq_partials(g, ws, part_off=0):
     """Deterministic sum-of-squares partials of the flat fp32 gradient ``g`` into ``ws[part_off:]``; returns how
     many partials were written (at most CLIP_PARTS).  ``ws`` is the CLIP_WS-float workspace."""
-    _clip_f32(g, 0, "sumsq_partials: g")
-    _clip_f32(ws, CLIP_WS, "sumsq_partials: workspace")
+    _vec(g, 0, "sumsq_partials: g")
+    _vec(ws, CLIP_WS, "sumsq_partials: workspace")
     _chk(g.device == ws.device, "sumsq_partials: g and workspace on different devices")
     nblk = min(max((g.numel() // 4 + 1 + 255) // 256, 1), CLIP_PARTS)
     _chk(0 <= part_off and part_off + nblk <= CLIP_WS,
@@ -1180,8 +1182,8 @@ def sumsq_partials(g, ws, part_off=0):
 def clip_coef(ws, nparts, max_norm, out, gscale=1.0, dev_scale=None):
     """``out[0:3]`` = [norm, clip coefficient, non-finite flag] from ``ws[:nparts]``: norm = |gscale * dev| *
     sqrt(sum), coefficient = dev * min(1, max_norm / (norm + 1e-6)), dev = ``dev_scale[0]`` (1 when None)."""
-    _clip_f32(ws, CLIP_WS, "clip_coef: workspace")
-    _clip_f32(out, 3, "clip_coef: out")
+    _vec(ws, CLIP_WS, "clip_coef: workspace")
+    _vec(out, 3, "clip_coef: out")
     _chk(1 <= nparts <= CLIP_WS, f"clip_coef: nparts={nparts}")
     if dev_scale is not None:
         _chk(dev_scale.dtype == F32 and dev_scale.is_cuda and dev_scale.numel() >= 1,
@@ -1255,13 +1257,6 @@ class LwTables:
         return torch.zeros(2 * self.nchunk, dtype=F32, device=dev), torch.zeros(3 * self.nseg, dtype=F32, device=dev)
 
 
-def _lw_vec(t, n, name, dtype=F32, optional=False):
-    if t is None and optional:
-        return
-    _chk(t is not None and t.dtype == dtype and t.is_cuda and t.dim() == 1 and t.is_contiguous() and t.numel() >= n,
-         f"{name}: expected a contiguous CUDA {dtype} vector of at least {n}")
-
-
 def _lw_scalar(t, name):
     if t is not None:
         _chk(t.dtype == F32 and t.is_cuda and t.numel() >= 1, f"{name} must be a CUDA fp32 scalar")
@@ -1279,8 +1274,8 @@ def lw_norm_partials(p, g, tab, partials, m=None, v=None, b1=0.9, b2=0.999, eps=
     _lw_tab(tab, "lw_norm_partials")
     lamb = m is not None or v is not None
     for t, nm in ((p, "p"), (g, "g")) + (((m, "m"), (v, "v")) if lamb else ()):
-        _lw_vec(t, tab.extent, f"lw_norm_partials: {nm}")
-    _lw_vec(partials, 2 * tab.nchunk, "lw_norm_partials: workspace")
+        _vec(t, tab.extent, f"lw_norm_partials: {nm}")
+    _vec(partials, 2 * tab.nchunk, "lw_norm_partials: workspace")
     _lw_scalar(gscale_dev, "lw_norm_partials: gscale_dev")
     call("pdnn_lw_norm_partials", ptr(p), ptr(g), ptr(m), ptr(v), ptr(tab.seg), ptr(tab.chk), tab.nseg, tab.nchunk,
          ptr(partials), int(lamb), float(b1), float(b2), 1.0 - float(b1), 1.0 - float(b2), float(eps), float(bc1), float(bc2), ptr(gscale_dev),
@@ -1291,8 +1286,8 @@ def lw_ratio(partials, tab, out, lamb, trust_coef=1e-3, eps=1e-8, clamp=False, g
     """One block per segment: ``out[0:nseg]`` trust ratios, ``out[nseg:2 nseg]`` ||w||, ``out[2 nseg:3 nseg]`` the
     other norm (LARS: |gscale| ||g||; LAMB: ||u||), from the chunk partials, added in table order in double."""
     _lw_tab(tab, "lw_ratio")
-    _lw_vec(partials, 2 * tab.nchunk, "lw_ratio: workspace")
-    _lw_vec(out, 3 * tab.nseg, "lw_ratio: out")
+    _vec(partials, 2 * tab.nchunk, "lw_ratio: workspace")
+    _vec(out, 3 * tab.nseg, "lw_ratio: out")
     _lw_scalar(gscale_dev, "lw_ratio: gscale_dev")
     call("pdnn_lw_ratio", ptr(partials), ptr(tab.seg), tab.nseg, tab.nchunk, int(lamb), float(trust_coef), float(eps),
          int(clamp), ptr(gscale_dev), float(gscale), ptr(out), stream())
@@ -1304,11 +1299,11 @@ def lars_apply(p, g, buf, shadow, tab, ratio, lr, momentum, dampening, nesterov,
     """p -= lr * momentum-recurrence(ratio[seg] * (gscale * g + wd_seg * p)) over the segments of ``tab``; refreshes
     ``shadow``.  ``hyper`` = [lr] overrides ``lr`` (graph replay)."""
     _lw_tab(tab, "lars_apply")
-    _lw_vec(p, tab.extent, "lars_apply: p")
-    _lw_vec(g, tab.extent, "lars_apply: g")
-    _lw_vec(buf, tab.extent, "lars_apply: momentum buffer", optional=momentum == 0)
-    _lw_vec(shadow, tab.extent, "lars_apply: shadow", dtype=BF16, optional=True)
-    _lw_vec(ratio, tab.nseg, "lars_apply: ratio")
+    _vec(p, tab.extent, "lars_apply: p")
+    _vec(g, tab.extent, "lars_apply: g")
+    _vec(buf, tab.extent, "lars_apply: momentum buffer", optional=momentum == 0)
+    _vec(shadow, tab.extent, "lars_apply: shadow", dtype=BF16, optional=True)
+    _vec(ratio, tab.nseg, "lars_apply: ratio")
     _lw_scalar(gscale_dev, "lars_apply: gscale_dev")
     call("pdnn_lars_apply", ptr(p), ptr(g), ptr(buf), ptr(shadow), ptr(tab.seg), ptr(tab.chk), tab.nseg, tab.nchunk,
          ptr(ratio), float(lr), float(momentum), float(dampening), int(nesterov), int(first), ptr(gscale_dev),
@@ -1320,9 +1315,9 @@ def lamb_apply(p, m, v, shadow, tab, ratio, lr, eps, bc1, bc2, hyper=None):
     ``shadow``.  ``hyper`` = [lr, 1-b1^t, 1-b2^t] overrides lr/bc1/bc2 (graph replay)."""
     _lw_tab(tab, "lamb_apply")
     for t, nm in ((p, "p"), (m, "m"), (v, "v")):
-        _lw_vec(t, tab.extent, f"lamb_apply: {nm}")
-    _lw_vec(shadow, tab.extent, "lamb_apply: shadow", dtype=BF16, optional=True)
-    _lw_vec(ratio, tab.nseg, "lamb_apply: ratio")
+        _vec(t, tab.extent, f"lamb_apply: {nm}")
+    _vec(shadow, tab.extent, "lamb_apply: shadow", dtype=BF16, optional=True)
+    _vec(ratio, tab.nseg, "lamb_apply: ratio")
     call("pdnn_lamb_apply", ptr(p), ptr(m), ptr(v), ptr(shadow), ptr(tab.seg), ptr(tab.chk), tab.nseg, tab.nchunk,
          ptr(ratio), float(lr), float(eps), float(bc1), float(bc2), ptr(hyper), stream())
 

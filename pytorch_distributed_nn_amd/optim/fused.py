@@ -12,6 +12,11 @@ that are not flat fall back to one launch per tensor (GPU) or the torch referenc
 ``set_grad_clip(max_norm)`` adds global-norm gradient clipping to the same step: two norm launches leave the
 clip coefficient in device memory and the update launch applies it (the gradient buffer is not rewritten).
 
+Every optimizer here is three pieces under the one ``step()`` of ``_FusedBase``: ``_begin_ranges`` (create the
+flat state, advance the step counter), ``_apply_range`` (the kernel launches) and ``_step_param`` (the same rule
+in torch ops).  The state and the torch-op recurrences of the two families live once, in ``_MomentumRule`` (SGD,
+LARS) and ``_MomentsRule`` (Adam, AdamW, LAMB).
+
 Reference parity: the PS master applies ``param -= lr * avg_grad`` (sync_replicas_master_nn.py:22-28,
 216-219) and ignores --momentum (defect D9); the C++ master fuses the average into the update as
 ``ApplyGrad(lr / count)`` (sync_replicas_master_nn.h:124-128); the TF stack uses Adam
@@ -37,6 +42,12 @@ def _flat_of(params):
     return (fp, rng) if rng is not None else (None, None)
 
 
+def _cut(t, a, b):
+    """``t[a:b]`` of an optional flat tensor; ``t`` itself when that is all of it (same pointer and length for the
+    kernel, and the step of a whole arena spends no host time on views)."""
+    return t if t is None or (a == 0 and b == t.numel()) else t[a:b]
+
+
 class _FusedBase(torch.optim.Optimizer):
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
@@ -53,6 +64,51 @@ class _FusedBase(torch.optim.Optimizer):
         if gi not in self._flat_cache:
             self._flat_cache[gi] = _flat_of(group["params"])
         return self._flat_cache[gi]
+
+    # ------------------------------------------------------------------------------------------ the step
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if self._consume_overlap():
+            return loss
+        gsd = self._clip_scale()
+        for gi, group in enumerate(self.param_groups):
+            fp, rng = self._group_flat(gi, group)
+            if fp is not None and fp.data.is_cuda:
+                state = self._begin_ranges(gi, group)
+                self._apply_range(gi, group, rng[0], rng[1], state, gsd, self._hyper[gi] if self._graph else None)
+                fp.generation += 1
+                continue
+            rows = [self._step_param(group, p, gsd) for p in group["params"] if p.grad is not None]
+            if rows and rows[0] is not None:         # LARS / LAMB: (ratio, ||w||, other norm) of every parameter
+                self._lw_loose[gi] = torch.stack([torch.stack(r) for r in rows], dim=1)
+        return loss
+
+    def _begin_ranges(self, gi, group):
+        """Host side, once per step of a flat group: create its state on first use and advance the step counter
+        (in graph mode ``pre_replay`` advances it).  Returns what ``_apply_range`` needs of it."""
+        raise NotImplementedError
+
+    def _apply_range(self, gi, group, a, b, state, gsd, hyper=None):
+        """The kernel launches that update flat-arena elements [a, b) of group ``gi``: the only caller of each
+        update kernel.  ``gsd`` is the device gradient scale, ``hyper`` the graph-mode device values."""
+        raise NotImplementedError
+
+    def _step_param(self, group, p, gsd):
+        """The same update of one parameter in torch ops (loose tensors, CPU arenas)."""
+        raise NotImplementedError
+
+    def _scaled_grad(self, p, gsd):
+        """The gradient as the update sees it: times ``grad_scale`` and the device scale / clip coefficient."""
+        g = p.grad
+        if self.grad_scale != 1.0:
+            g = g * self.grad_scale
+        if gsd is not None:
+            g = g * gsd.to(g.device).reshape(())
+        return g
 
     # ------------------------------------------------------------------------------- gradient clipping
     def set_grad_clip(self, max_norm: float | None):
@@ -151,9 +207,6 @@ class _FusedBase(torch.optim.Optimizer):
     def _check_graphable(self, gi):
         pass
 
-    def _hyper_buf(self, gi, n, device):
-        return self._hyper[gi]
-
     def _hyper_values(self, gi, group, advance=True):    # one step's values, in the kernel's hyper[] order
         return [group["lr"]]
 
@@ -193,18 +246,12 @@ class _FusedBase(torch.optim.Optimizer):
     @torch.no_grad()
     def _overlap_range(self, a, b):
         """Update flat-arena elements [a, b) (a bucket) with the state _overlap_begin prepared (current stream)."""
-        self._apply_range(0, self.param_groups[0], a, b, self._ovl_state)
+        self._apply_range(0, self.param_groups[0], a, b, self._ovl_state, self.grad_scale_dev)
 
     def _overlap_end(self):
         fp, _ = self._group_flat(0, self.param_groups[0])
         fp.generation += 1
         self._ovl_done = True          # the next step() finds the update applied
-
-    def _begin_ranges(self, gi, group):
-        raise NotImplementedError
-
-    def _apply_range(self, gi, group, a, b, state):
-        raise NotImplementedError
 
     def _consume_overlap(self):
         if getattr(self, "_ovl_done", False):
@@ -229,89 +276,40 @@ class _FusedBase(torch.optim.Optimizer):
                         p.grad.zero_()
 
 
-class SGD(_FusedBase):
-    def __init__(self, params, lr=0.01, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False):
-        if nesterov and (momentum <= 0 or dampening != 0):
-            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
-                                      nesterov=nesterov))
+class _MomentumRule:
+    """State and torch-op recurrence of the momentum family (SGD, LARS); mixed in ahead of the optimizer base."""
 
     def _check_graphable(self, gi):
         # the first momentum step initialises the buffer (a different kernel branch): run it eagerly
         if self.param_groups[gi]["momentum"] != 0 and "momentum_buffer" not in self.state.get(f"flat{gi}", {}):
-            raise RuntimeError("SGD graph mode: run one eager step before capture (momentum buffer init)")
+            raise RuntimeError(f"{type(self).__name__} graph mode: run one eager step before capture "
+                               "(momentum buffer init)")
 
-    def _begin_ranges(self, gi, group):
-        fp, (s, e) = self._group_flat(gi, group)
-        st = self.state.setdefault(f"flat{gi}", {})
+    def _begin_ranges(self, gi, group):         # -> (momentum buffer of the range or None, first step)
+        st = self.state[f"flat{gi}"]
         first = "momentum_buffer" not in st
         if group["momentum"] != 0 and first:
+            fp, (s, e) = self._group_flat(gi, group)
             st["momentum_buffer"] = torch.zeros(e - s, device=fp.data.device)
-        return first
+        return st.get("momentum_buffer"), first
 
-    def _apply_range(self, gi, group, a, b, first):
-        from ..ops import kernels as K
-        fp, (s, _) = self._group_flat(gi, group)
-        buf = self.state[f"flat{gi}"].get("momentum_buffer")
-        K.sgd_step(fp.data[a:b], fp.grad[a:b], None if buf is None else buf[a - s:b - s],
-                   fp.shadow[a:b] if fp.shadow is not None else None, group["lr"], group["momentum"],
-                   group["dampening"], group["weight_decay"], group["nesterov"], self.grad_scale_dev,
-                   self.grad_scale, first)
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        if self._consume_overlap():
-            return loss
-        gsd = self._clip_scale()
-        for gi, group in enumerate(self.param_groups):
-            lr, mom, damp, wd, nest = (group["lr"], group["momentum"], group["dampening"], group["weight_decay"],
-                                       group["nesterov"])
-            fp, rng = self._group_flat(gi, group)
-            if fp is not None and fp.data.is_cuda:
-                from ..ops import kernels as K
-                s, e = rng
-                st = self.state.setdefault(f"flat{gi}", {})
-                first = "momentum_buffer" not in st
-                if mom != 0 and first:
-                    st["momentum_buffer"] = torch.zeros(e - s, device=fp.data.device)
-                buf = st.get("momentum_buffer")
-                hyper = self._hyper_buf(gi, 1, fp.data.device) if self._graph else None
-                K.sgd_step(fp.data[s:e], fp.grad[s:e], buf, fp.shadow[s:e] if fp.shadow is not None else None,
-                           lr, mom, damp, wd, nest, gsd, self.grad_scale, first, hyper=hyper)
-                fp.generation += 1
-                continue
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                g = p.grad
-                if self.grad_scale != 1.0:
-                    g = g * self.grad_scale
-                if gsd is not None:
-                    g = g * gsd.to(g.device)
-                if wd != 0:
-                    g = g.add(p, alpha=wd)
-                if mom != 0:
-                    st = self.state[p]
-                    if "momentum_buffer" not in st:
-                        st["momentum_buffer"] = g.clone().detach()
-                    else:
-                        st["momentum_buffer"].mul_(mom).add_(g, alpha=1 - damp)
-                    b = st["momentum_buffer"]
-                    g = g.add(b, alpha=mom) if nest else b
-                p.add_(g, alpha=-lr)
-        return loss
+    def _momentum(self, group, p, d):
+        """torch.optim.SGD's momentum / dampening / Nesterov recurrence on the direction ``d`` of parameter ``p``."""
+        mom = group["momentum"]
+        if mom == 0:
+            return d
+        st = self.state[p]
+        if "momentum_buffer" not in st:
+            st["momentum_buffer"] = d.clone().detach()
+        else:
+            st["momentum_buffer"].mul_(mom).add_(d, alpha=1 - group["dampening"])
+        b = st["momentum_buffer"]
+        return d.add(b, alpha=mom) if group["nesterov"] else b
 
 
-class Adam(_FusedBase):
-    decoupled = False
-
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-
+class _MomentsRule:
+    """State, graph-mode values and torch-op moment update of the Adam family (Adam, AdamW, LAMB); mixed in ahead
+    of the optimizer base."""
     _HYPER_LEN = 3
 
     def _hyper_values(self, gi, group, advance=True):
@@ -322,79 +320,80 @@ class Adam(_FusedBase):
         b1, b2 = group["betas"]
         return [group["lr"], 1 - b1 ** t, 1 - b2 ** t]
 
-    def _begin_ranges(self, gi, group):
-        fp, (s, e) = self._group_flat(gi, group)
-        st = self.state.setdefault(f"flat{gi}", {})
+    def _begin_ranges(self, gi, group):         # -> (m, v of the range, step count t)
+        st = self.state[f"flat{gi}"]
         if "step" not in st:
+            fp, (s, e) = self._group_flat(gi, group)
             st["step"] = 0
             st["exp_avg"] = torch.zeros(e - s, device=fp.data.device)
             st["exp_avg_sq"] = torch.zeros(e - s, device=fp.data.device)
-        st["step"] += 1
-        return max(st["step"], 1)
+        if not self._graph:                      # in graph mode t advances in pre_replay(); kernels read hyper[]
+            st["step"] += 1
+        return st["exp_avg"], st["exp_avg_sq"], max(st["step"], 1)
 
-    def _apply_range(self, gi, group, a, b, t):
+    def _moments(self, group, p, g):
+        """Advance the moments of parameter ``p`` by the gradient ``g``; returns (m, sqrt(v / (1 - b2^t)) + eps,
+        1 - b1^t), in torch.optim.Adam's operation order."""
+        b1, b2 = group["betas"]
+        st = self.state[p]
+        if "step" not in st:
+            st["step"] = 0
+            st["exp_avg"] = torch.zeros_like(p)
+            st["exp_avg_sq"] = torch.zeros_like(p)
+        st["step"] += 1
+        t = st["step"]
+        st["exp_avg"].lerp_(g, 1 - b1)
+        st["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1 - b2)
+        denom = (st["exp_avg_sq"].sqrt() / math.sqrt(1 - b2 ** t)).add_(group["eps"])
+        return st["exp_avg"], denom, 1 - b1 ** t
+
+
+class SGD(_MomentumRule, _FusedBase):
+    def __init__(self, params, lr=0.01, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False):
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                      nesterov=nesterov))
+
+    def _apply_range(self, gi, group, a, b, state, gsd, hyper=None):
         from ..ops import kernels as K
         fp, (s, _) = self._group_flat(gi, group)
-        st = self.state[f"flat{gi}"]
-        (b1, b2) = group["betas"]
-        K.adam_step(fp.data[a:b], fp.grad[a:b], st["exp_avg"][a - s:b - s], st["exp_avg_sq"][a - s:b - s],
-                    fp.shadow[a:b] if fp.shadow is not None else None, group["lr"], b1, b2, group["eps"],
-                    group["weight_decay"], self.decoupled, 1 - b1 ** t, 1 - b2 ** t, self.grad_scale_dev,
-                    self.grad_scale)
+        buf, first = state
+        K.sgd_step(_cut(fp.data, a, b), _cut(fp.grad, a, b), _cut(buf, a - s, b - s), _cut(fp.shadow, a, b),
+                   group["lr"], group["momentum"], group["dampening"], group["weight_decay"], group["nesterov"],
+                   gsd, self.grad_scale, first, hyper=hyper)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        if self._consume_overlap():
-            return loss
-        gsd = self._clip_scale()
-        for gi, group in enumerate(self.param_groups):
-            lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
-            fp, rng = self._group_flat(gi, group)
-            if fp is not None and fp.data.is_cuda:
-                from ..ops import kernels as K
-                s, e = rng
-                st = self.state.setdefault(f"flat{gi}", {})
-                if "step" not in st:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros(e - s, device=fp.data.device)
-                    st["exp_avg_sq"] = torch.zeros(e - s, device=fp.data.device)
-                hyper = None
-                if self._graph:                  # t advances in pre_replay(); kernel reads hyper[]
-                    hyper = self._hyper_buf(gi, 3, fp.data.device)
-                else:
-                    st["step"] += 1
-                t = max(st["step"], 1)
-                K.adam_step(fp.data[s:e], fp.grad[s:e], st["exp_avg"], st["exp_avg_sq"],
-                            fp.shadow[s:e] if fp.shadow is not None else None, lr, b1, b2, eps, wd,
-                            self.decoupled, 1 - b1 ** t, 1 - b2 ** t, gsd, self.grad_scale, hyper=hyper)
-                fp.generation += 1
-                continue
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                g = p.grad * self.grad_scale
-                if gsd is not None:
-                    g = g * gsd.to(g.device)
-                st = self.state[p]
-                if "step" not in st:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p)
-                    st["exp_avg_sq"] = torch.zeros_like(p)
-                st["step"] += 1
-                t = st["step"]
-                if self.decoupled:
-                    p.mul_(1 - lr * wd)
-                elif wd:
-                    g = g.add(p, alpha=wd)
-                st["exp_avg"].lerp_(g, 1 - b1)
-                st["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1 - b2)
-                denom = (st["exp_avg_sq"].sqrt() / math.sqrt(1 - b2 ** t)).add_(eps)    # torch.optim.Adam's order
-                p.addcdiv_(st["exp_avg"], denom, value=-lr / (1 - b1 ** t))
-        return loss
+    def _step_param(self, group, p, gsd):
+        g = self._scaled_grad(p, gsd)
+        if group["weight_decay"] != 0:
+            g = g.add(p, alpha=group["weight_decay"])
+        p.add_(self._momentum(group, p, g), alpha=-group["lr"])
+
+
+class Adam(_MomentsRule, _FusedBase):
+    decoupled = False
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+
+    def _apply_range(self, gi, group, a, b, state, gsd, hyper=None):
+        from ..ops import kernels as K
+        fp, (s, _) = self._group_flat(gi, group)
+        m, v, t = state
+        b1, b2 = group["betas"]
+        K.adam_step(_cut(fp.data, a, b), _cut(fp.grad, a, b), _cut(m, a - s, b - s), _cut(v, a - s, b - s),
+                    _cut(fp.shadow, a, b), group["lr"], b1, b2, group["eps"], group["weight_decay"], self.decoupled,
+                    1 - b1 ** t, 1 - b2 ** t, gsd, self.grad_scale, hyper=hyper)
+
+    def _step_param(self, group, p, gsd):
+        lr, wd = group["lr"], group["weight_decay"]
+        g = self._scaled_grad(p, gsd)
+        if self.decoupled:
+            p.mul_(1 - lr * wd)
+        elif wd:
+            g = g.add(p, alpha=wd)
+        m, denom, bc1 = self._moments(group, p, g)
+        p.addcdiv_(m, denom, value=-lr / bc1)
 
 
 class AdamW(Adam):
@@ -420,7 +419,6 @@ class _LayerwiseBase(_FusedBase):
     ``exclude(p)`` -> True leaves a parameter out of weight decay and out of the scaling (ratio 1); ``None`` adapts
     and decays everything.  ``trust_ratios(gi)`` / ``param_norms(gi)`` / ``update_norms(gi)`` return the last
     step's per-parameter values of group ``gi``, in group order, as a device vector (no sync)."""
-    _LAMB = False
 
     def __init__(self, params, defaults, exclude):
         super().__init__(params, defaults)
@@ -499,34 +497,8 @@ class _LayerwiseBase(_FusedBase):
             r = torch.where(r > 1, torch.ones_like(r), r)
         return torch.where((wn == 0) | (un == 0), torch.ones_like(wn), r)
 
-    def _scaled_grad(self, p, gsd):
-        g = p.grad
-        if self.grad_scale != 1.0:
-            g = g * self.grad_scale
-        if gsd is not None:
-            g = g * gsd.to(g.device).reshape(())
-        return g
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        gsd = self._clip_scale()
-        for gi, group in enumerate(self.param_groups):
-            fp, rng = self._group_flat(gi, group)
-            if fp is not None and fp.data.is_cuda:
-                self._step_fused(gi, group, fp, rng, gsd)
-                fp.generation += 1
-                continue
-            rows = [self._step_param(group, p, gsd) for p in group["params"] if p.grad is not None]
-            if rows:
-                self._lw_loose[gi] = torch.stack([torch.stack(r) for r in rows], dim=1)
-        return loss
-
-
-class LARS(_LayerwiseBase):
+class LARS(_MomentumRule, _LayerwiseBase):
     """Layer-wise adaptive rate scaling (You, Gitman, Ginsburg 2017) on SGD's momentum recurrence:
 
         r = trust_coef * ||w|| / (||g|| + wd * ||w|| + eps)        (g as the update sees it: scaled, clipped)
@@ -542,103 +514,61 @@ class LARS(_LayerwiseBase):
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                                       nesterov=nesterov, trust_coef=trust_coef, eps=eps, clamp=clamp), exclude)
 
-    def _check_graphable(self, gi):
-        if self.param_groups[gi]["momentum"] != 0 and "momentum_buffer" not in self.state.get(f"flat{gi}", {}):
-            raise RuntimeError("LARS graph mode: run one eager step before capture (momentum buffer init)")
-
-    def _step_fused(self, gi, group, fp, rng, gsd):
+    def _apply_range(self, gi, group, s, e, state, gsd, hyper=None):        # always the group's whole range
         from ..ops import kernels as K
-        s, e = rng
+        fp, _ = self._group_flat(gi, group)
         lw = self._lw_prepare(gi, group)
-        st = self.state.setdefault(f"flat{gi}", {})
-        first = "momentum_buffer" not in st
-        if group["momentum"] != 0 and first:
-            st["momentum_buffer"] = torch.zeros(e - s, device=fp.data.device)
-        hyper = self._hyper_buf(gi, 1, fp.data.device) if self._graph else None
+        buf, first = state
         tab, n = lw["tab"], lw["tab"].nseg
-        p, g = fp.data[s:e], fp.grad[s:e]
+        p, g = _cut(fp.data, s, e), _cut(fp.grad, s, e)
         K.lw_norm_partials(p, g, tab, lw["ws"], gscale_dev=gsd, gscale=self.grad_scale)
         K.lw_ratio(lw["ws"], tab, lw["out"], False, group["trust_coef"], group["eps"], group["clamp"], gsd,
                    self.grad_scale)
-        K.lars_apply(p, g, st.get("momentum_buffer"), fp.shadow[s:e] if fp.shadow is not None else None, tab,
-                     lw["out"][:n], group["lr"], group["momentum"], group["dampening"], group["nesterov"], gsd,
-                     self.grad_scale, first, hyper=hyper)
+        K.lars_apply(p, g, buf, _cut(fp.shadow, s, e), tab, lw["out"][:n], group["lr"], group["momentum"],
+                     group["dampening"], group["nesterov"], gsd, self.grad_scale, first, hyper=hyper)
 
     def _step_param(self, group, p, gsd):
-        lr, mom, damp, nest = group["lr"], group["momentum"], group["dampening"], group["nesterov"]
         ex = self._excluded(p)
         wd = 0.0 if ex else group["weight_decay"]
         g = self._scaled_grad(p, gsd)
         wn, un = torch.linalg.vector_norm(p), torch.linalg.vector_norm(g)
         r = self._ratio(wn, un, group["trust_coef"] * wn / (un + wd * wn + group["eps"]), not ex, group["clamp"])
         d = (g.add(p, alpha=wd) if wd != 0 else g) * r
-        if mom != 0:
-            st = self.state[p]
-            if "momentum_buffer" not in st:
-                st["momentum_buffer"] = d.clone().detach()
-            else:
-                st["momentum_buffer"].mul_(mom).add_(d, alpha=1 - damp)
-            b = st["momentum_buffer"]
-            d = d.add(b, alpha=mom) if nest else b
-        p.add_(d, alpha=-lr)
+        p.add_(self._momentum(group, p, d), alpha=-group["lr"])
         return r, wn, un
 
 
-class LAMB(_LayerwiseBase):
+class LAMB(_MomentsRule, _LayerwiseBase):
     """Layer-wise adaptive moments (You et al. 2020): Adam's moments m, v of the gradient as the update sees it,
 
         u = (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps) + wd * w;     r = ||w|| / ||u||;     w -= lr * r * u
 
     per parameter; r = 1 for an excluded parameter (which also gets no weight decay), when ||w|| = 0 or ||u|| = 0;
     ``clamp`` caps r at 1."""
-    _LAMB = True
-    _HYPER_LEN = 3
-    _hyper_values = Adam._hyper_values
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, clamp=False,
                  exclude=_exclude_1d):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clamp=clamp), exclude)
 
-    def _step_fused(self, gi, group, fp, rng, gsd):
+    def _apply_range(self, gi, group, s, e, state, gsd, hyper=None):        # always the group's whole range
         from ..ops import kernels as K
-        s, e = rng
+        fp, _ = self._group_flat(gi, group)
         lw = self._lw_prepare(gi, group)
-        st = self.state.setdefault(f"flat{gi}", {})
-        if "step" not in st:
-            st["step"] = 0
-            st["exp_avg"] = torch.zeros(e - s, device=fp.data.device)
-            st["exp_avg_sq"] = torch.zeros(e - s, device=fp.data.device)
-        hyper = None
-        if self._graph:                          # t advances in pre_replay(); the kernels read hyper[]
-            hyper = self._hyper_buf(gi, 3, fp.data.device)
-        else:
-            st["step"] += 1
-        t = max(st["step"], 1)
+        m, v, t = state
         (b1, b2), eps = group["betas"], group["eps"]
         bc1, bc2 = 1 - b1 ** t, 1 - b2 ** t
         tab, n = lw["tab"], lw["tab"].nseg
-        p, m, v = fp.data[s:e], st["exp_avg"], st["exp_avg_sq"]
-        K.lw_norm_partials(p, fp.grad[s:e], tab, lw["ws"], m, v, b1, b2, eps, bc1, bc2, gsd, self.grad_scale,
+        p = _cut(fp.data, s, e)
+        K.lw_norm_partials(p, _cut(fp.grad, s, e), tab, lw["ws"], m, v, b1, b2, eps, bc1, bc2, gsd, self.grad_scale,
                            hyper=hyper)
         K.lw_ratio(lw["ws"], tab, lw["out"], True, clamp=group["clamp"])
-        K.lamb_apply(p, m, v, fp.shadow[s:e] if fp.shadow is not None else None, tab, lw["out"][:n], group["lr"],
-                     eps, bc1, bc2, hyper=hyper)
+        K.lamb_apply(p, m, v, _cut(fp.shadow, s, e), tab, lw["out"][:n], group["lr"], eps, bc1, bc2, hyper=hyper)
 
     def _step_param(self, group, p, gsd):
-        (b1, b2), eps = group["betas"], group["eps"]
         ex = self._excluded(p)
         wd = 0.0 if ex else group["weight_decay"]
-        g = self._scaled_grad(p, gsd)
-        st = self.state[p]
-        if "step" not in st:
-            st["step"] = 0
-            st["exp_avg"] = torch.zeros_like(p)
-            st["exp_avg_sq"] = torch.zeros_like(p)
-        st["step"] += 1
-        t = st["step"]
-        st["exp_avg"].lerp_(g, 1 - b1)
-        st["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1 - b2)
-        u = (st["exp_avg"] / (1 - b1 ** t)) / ((st["exp_avg_sq"].sqrt() / math.sqrt(1 - b2 ** t)).add_(eps))
+        m, denom, bc1 = self._moments(group, p, self._scaled_grad(p, gsd))
+        u = (m / bc1) / denom
         if wd != 0:
             u = u.add(p, alpha=wd)
         wn, un = torch.linalg.vector_norm(p), torch.linalg.vector_norm(u)
