@@ -22,6 +22,22 @@
 //   attn_bwd_dq:   one block = 64 queries (4 waves x 16 queries), loop over key tiles k <= query:
 //       S^T = K Q^T, P^T, dP^T = V dO^T, dS^T, dQ^T += K^T dS^T
 //   delta[q] = sum_d dO[q][d] O[q][d] comes from attn_bwd_delta.
+//
+// Packed documents (template parameter DOC; the plain instantiations compile to the code they had before it existed,
+// profiles/attention_doc_mask.txt): query q of sequence b sees key k iff doc_start[b][q] <= k <= q.  doc_start[b][t] is
+// the first token of t's document, doc_end[b][t] one past its last; both int32 [B][T], non-decreasing in t, and every
+// value is clamped into [0, T] before it becomes a tile index or an address (a malformed array gives wrong numbers,
+// never an out-of-range access).  Tile ranges follow the bounds from both sides: the key loops of the forward and of
+// dQ start at the tile of the block's first doc_start, a wave skips a tile wholly before the doc_start of its first
+// query, and the document mask runs only on "edge" tiles (k0 < doc_start of the wave's last query; wave-uniform, like
+// diag).  The query loop of dK / dV ends at the tile of the doc_end of the block's last key, a wave skips a tile at or
+// past the doc_end of its last key, and masks only tiles that reach the doc_end of its first key.  On an edge tile of
+// the forward a query may have every key masked while its running maximum is still -inf (queries 96..127 with documents
+// starting at 60 and 100: query 100 in key tile 0); the DOC forward therefore starts the maximum at a finite floor
+// (see there), which gives p = 0 with l and m unchanged on such a tile and costs no tile anything.
+// The block order stays heavy-causal-first (late query tiles, early key tiles).  With short documents that is no longer
+// the order of decreasing work (a late query tile may hold one short document); a work-sorted order is left for a
+// measured follow-up.
 #include "common.h"
 #include "tuning.h"
 
@@ -50,6 +66,17 @@ __device__ __forceinline__ void attn_block(int ntile, int H, bool heavy_is_last,
 #endif
 }
 constexpr int NTA = 256;
+
+// the last kernel argument: ``int causal`` of the plain kernels, the two bound arrays of the DOC ones
+struct DocArg {
+    const int* start;           // doc_start [B][T]
+    const int* end;             // doc_end [B][T]
+};
+template <bool DOC> struct MaskSel { typedef int type; };
+template <> struct MaskSel<true> { typedef DocArg type; };
+__device__ __forceinline__ int mask_causal(int causal) { return causal; }
+__device__ __forceinline__ int mask_causal(const DocArg&) { return 1; }
+__device__ __forceinline__ int clamp_t(int v, int T) { return min(max(v, 0), T); }
 constexpr float RESC = 8.f;     // forward lazy-rescale threshold (log2 units)
 constexpr float LOG2E = 1.4426950408889634f;
 
@@ -138,8 +165,11 @@ __device__ __forceinline__ float rmax4(float v) { return pl32(pl16(v, true), tru
 __device__ __forceinline__ float rsum4(float v) { return pl32(pl16(v, false), false); }
 
 // ---------------------------------------------------------------------------------------------- forward
+template <bool DOC>
 __global__ void __launch_bounds__(NTA) attn_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
-                                                       float* __restrict__ lse2, int T, int H, float scale, int causal) {
+                                                       float* __restrict__ lse2, int T, int H, float scale,
+                                                       typename MaskSel<DOC>::type mk) {
+    const int causal = mask_causal(mk);
     __shared__ __attribute__((aligned(16))) bf16_t smem[2][2][64 * HD];     // [buf][K|V]
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4;
     const int nqb = T / 128;
@@ -164,31 +194,47 @@ __global__ void __launch_bounds__(NTA) attn_fwd_kernel(const bf16_t* __restrict_
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) o[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    float m[2] = {-INFINITY, -INFINITY}, l[2] = {0.f, 0.f};
+    // DOC: the running maximum starts at a finite floor, not -inf.  A plain wave's first tile holds a visible key for
+    // every query (key 0 is in tile 0); with documents it need not (queries 96..127, documents from 60 and 100: query
+    // 100 has key tile 0 fully masked), and with m = -inf that tile would form exp2(fmaf(-inf, c, +inf)) = NaN.  From the
+    // floor the same tile gives p = exp2(-inf) = 0 and alpha = exp2(0) = 1: l and m unchanged, at no cost on any tile;
+    // the first visible key then moves m exactly as from -inf (alpha = exp2(floor - m) = 0 on l = 0, O = 0).
+    constexpr float M0 = DOC ? -3.0e38f : -INFINITY;
+    float m[2] = {M0, M0}, l[2] = {0.f, 0.f};
 
     const int nkb = causal ? (qb * 128 + 128) / 64 : T / 64;
+    // DOC: first key tile of the block, doc_start of the wave's first / last query (wave-uniform), of this lane's queries
+    int kb0 = 0, ws_first = 0, ws_last = 0, dsl[2] = {0, 0};
+    if constexpr (DOC) {
+        const int* ds = mk.start + (long)b * T;
+        kb0 = min(clamp_t(ds[qb * 128], T) >> 6, nkb - 1);
+        ws_first = __builtin_amdgcn_readfirstlane(clamp_t(ds[q0], T));
+        ws_last = __builtin_amdgcn_readfirstlane(clamp_t(ds[q0 + 31], T));
+#pragma unroll
+        for (int f = 0; f < 2; ++f) dsl[f] = clamp_t(ds[q0 + 16 * f + (lane & 15)], T) - 4 * g;    // for key row 4 g + r
+    }
     // K/V tiles: prefetch distance 2 (two register stages + two LDS buffers).  The per-tile compute of a
     // d=64 head is short, so with distance 1 every iteration waited out most of a global-load round trip
     // (causal and full attention took the same time: latency-, not throughput-bound).
     TileLd ka, va, kn, vn;
-    ka.load(Kp, ld, tid);
-    va.load(Vp, ld, tid);
+    ka.load(Kp + (long)kb0 * 64 * ld, ld, tid);
+    va.load(Vp + (long)kb0 * 64 * ld, ld, tid);
     ka.store(smem[0][0], tid);
     va.store(smem[0][1], tid);
-    if (nkb > 1) {
-        kn.load(Kp + 64L * ld, ld, tid);
-        vn.load(Vp + 64L * ld, ld, tid);
+    if (kb0 + 1 < nkb) {
+        kn.load(Kp + (long)(kb0 + 1) * 64 * ld, ld, tid);
+        vn.load(Vp + (long)(kb0 + 1) * 64 * ld, ld, tid);
     }
     __syncthreads();
-    // tile kb is in LDS buffer kb & 1; (hk, hv) hold tile kb + 1 in flight; (fk, fv) are free for kb + 2
-    auto step = [&](const int kb, TileLd& hk, TileLd& hv, TileLd& fk, TileLd& fv) {
-        const int cur = kb & 1;
+    // tile kb is in LDS buffer cur = (kb - kb0) & 1; (hk, hv) hold tile kb + 1 in flight; (fk, fv) are free for kb + 2
+    auto step = [&](const int kb, const int cur, TileLd& hk, TileLd& hv, TileLd& fk, TileLd& fv) {
         if (kb + 2 < nkb) {
             fk.load(Kp + (long)(kb + 2) * 64 * ld, ld, tid);
             fv.load(Vp + (long)(kb + 2) * 64 * ld, ld, tid);
         }
         const int k0 = kb * 64;
-        if (!causal || k0 <= q0 + 31) {              // wave-uniform: tile not entirely above the diagonal
+        // wave-uniform: tile not entirely above the diagonal (DOC: nor entirely before the wave's first document)
+        if ((!causal || k0 <= q0 + 31) && (!DOC || k0 + 63 >= ws_first)) {
             const bf16_t* Ki = smem[cur][0];
             const bf16_t* Vi = smem[cur][1];
             f32x4_t s[4][2];
@@ -216,6 +262,19 @@ __global__ void __launch_bounds__(NTA) attn_fwd_kernel(const bf16_t* __restrict_
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
                             if (k0 + 16 * kf + 4 * g + r > qi) s[kf][f][r] = -INFINITY;
+                }
+            }
+            if constexpr (DOC) {
+                if (k0 < ws_last) {                  // wave-uniform "edge": some query's document starts inside or after
+#pragma unroll
+                    for (int f = 0; f < 2; ++f) {
+                        const int lim = dsl[f] - k0;        // key k0 + 16 kf + 4 g + r is before the document
+#pragma unroll
+                        for (int kf = 0; kf < 4; ++kf)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                if (16 * kf + r < lim) s[kf][f][r] = -INFINITY;
+                    }
                 }
             }
 #pragma unroll
@@ -267,9 +326,9 @@ __global__ void __launch_bounds__(NTA) attn_fwd_kernel(const bf16_t* __restrict_
         }
         __syncthreads();
     };
-    for (int kb = 0; kb < nkb; kb += 2) {            // unrolled by 2: register stages are compile-time
-        step(kb, kn, vn, ka, va);
-        if (kb + 1 < nkb) step(kb + 1, ka, va, kn, vn);
+    for (int kb = kb0; kb < nkb; kb += 2) {          // unrolled by 2: register stages are compile-time
+        step(kb, 0, kn, vn, ka, va);
+        if (kb + 1 < nkb) step(kb + 1, 1, ka, va, kn, vn);
     }
     // lane holds O^T[d = 16 df + 4 g + r][q = q0 + 16 f + (lane & 15)]
 #pragma unroll
@@ -315,11 +374,12 @@ __global__ void __launch_bounds__(NTA) attn_bwd_delta_kernel(const bf16_t* __res
 
 // dK, dV for 64 NF keys per block (wave w: NF 16-key fragments from k0 = 64 NF kb + 16 NF w); loop over 64-query
 // tiles.  NF = 2 reads every Q / dO fragment out of LDS once for two key fragments (see attn_bwd_dq_kernel).
-template <int NF>
+template <int NF, bool DOC>
 __global__ void __launch_bounds__(NTA) attn_bwd_dkdv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dO,
                                                             const float* __restrict__ lse2, const float* __restrict__ delta,
                                                             bf16_t* __restrict__ dqkv, int T, int H, float scale,
-                                                            int causal) {
+                                                            typename MaskSel<DOC>::type mk) {
+    const int causal = mask_causal(mk);
     __shared__ __attribute__((aligned(16))) bf16_t smem[2][2][64 * HD];     // [buf][Q|dO]
     // the query tile's lse2 / delta ride along with its Q / dO tile through LDS: loaded from global memory in the
     // compute loop they were waited on behind the next tile's prefetch loads (vmcnt is in order), every tile
@@ -354,7 +414,18 @@ __global__ void __launch_bounds__(NTA) attn_bwd_dkdv_kernel(const bf16_t* __rest
         for (int i = 0; i < 4; ++i) dv[f][i] = dk[f][i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     const int qb0 = causal ? kb * NF : 0;            // first query tile that reaches this block's first key
-    const int nqb = T / 64;
+    int nqb = T / 64;
+    // DOC: the query loop ends with the document of the block's last key; doc_end of the wave's first / last key
+    // (wave-uniform) and of this lane's keys
+    int we_first = 0, we_last = 0, del[NF];
+    if constexpr (DOC) {
+        const int* de = mk.end + (long)b * T;
+        nqb = max(min((clamp_t(de[kb * 64 * NF + 64 * NF - 1], T) + 63) >> 6, nqb), qb0 + 1);
+        we_first = __builtin_amdgcn_readfirstlane(clamp_t(de[k0], T));
+        we_last = __builtin_amdgcn_readfirstlane(clamp_t(de[k0 + 16 * NF - 1], T));
+#pragma unroll
+        for (int f = 0; f < NF; ++f) del[f] = clamp_t(de[k0 + 16 * f + (lane & 15)], T) - 4 * g;   // for query row 4 g + r
+    }
     // threads 0-15 move the tile's lse2, 16-31 its delta (one float4 each)
     const float* lsrc = tid < 16 ? L2 + 4 * tid : Dl + 4 * (tid - 16);
     float4 lrow = {0.f, 0.f, 0.f, 0.f};
@@ -378,7 +449,7 @@ __global__ void __launch_bounds__(NTA) attn_bwd_dkdv_kernel(const bf16_t* __rest
             if (tid < 32) lrow = *reinterpret_cast<const float4*>(lsrc + (qb + 1) * 64);
         }
         const int qs = qb * 64;
-        if (!causal || qs + 63 >= k0) {
+        if ((!causal || qs + 63 >= k0) && (!DOC || qs < we_last)) {
             const bf16_t* Qi = smem[cur][0];
             const bf16_t* Oi = smem[cur][1];
             // S[q][key], dP[q][key]: lane holds rows q = qs + 16 qi + 4 g + r, column key = k0 + 16 f + (lane & 15)
@@ -398,6 +469,7 @@ __global__ void __launch_bounds__(NTA) attn_bwd_dkdv_kernel(const bf16_t* __rest
                 }
             }
             const bool diag = causal && qs < k0 + 16 * NF;  // wave-uniform: only these tiles need the mask
+            const bool edge = DOC && qs + 63 >= we_first;   // wave-uniform: the tile reaches past some key's document
 #pragma unroll
             for (int qi = 0; qi < 4; ++qi) {
                 const int qr = qs + 16 * qi + 4 * g;
@@ -413,6 +485,14 @@ __global__ void __launch_bounds__(NTA) attn_bwd_dkdv_kernel(const bf16_t* __rest
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
                             if (kl > qr + r) s[f][qi][r] = 0.f;
+                    }
+                    if constexpr (DOC) {
+                        if (edge) {
+                            const int lim = del[f] - qs;    // query qs + 16 qi + 4 g + r is past the document
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                if (16 * qi + r >= lim) s[f][qi][r] = 0.f;
+                        }
                     }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) dp[f][qi][r] = s[f][qi][r] * (dp[f][qi][r] - da[r]);
@@ -475,12 +555,13 @@ __global__ void __launch_bounds__(NTA) attn_bwd_dkdv_kernel(const bf16_t* __rest
 // per tile came with 24 KB of LDS reads, which saturated the LDS array (256 B/clk/CU) at the MFMA rate.
 // DELTA: the block also forms delta = rowsum(dO . O) of its queries (the four 16-lane groups of a query row take
 // 16 dims each) and writes it for attn_bwd_dkdv_kernel, which then runs after it: no separate delta launch
-template <bool DELTA, int NF>
+template <bool DELTA, int NF, bool DOC>
 __global__ void __launch_bounds__(NTA) attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dO,
                                                           const float* __restrict__ lse2, float* __restrict__ delta,
                                                           const bf16_t* __restrict__ o,
                                                           bf16_t* __restrict__ dqkv, int T, int H, float scale,
-                                                          int causal) {
+                                                          typename MaskSel<DOC>::type mk) {
+    const int causal = mask_causal(mk);
     __shared__ __attribute__((aligned(16))) bf16_t smem[2][2][64 * HD];     // [buf][K|V]
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4;
     const int nqb = T / (64 * NF);
@@ -534,21 +615,31 @@ __global__ void __launch_bounds__(NTA) attn_bwd_dq_kernel(const bf16_t* __restri
         for (int i = 0; i < 4; ++i) dq[f][i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     const int nkb = causal ? (qb + 1) * NF : T / 64;
+    // DOC: as in the forward, per 16 NF-query wave
+    int kb0 = 0, ws_first = 0, ws_last = 0, dsl[NF];
+    if constexpr (DOC) {
+        const int* ds = mk.start + (long)b * T;
+        kb0 = min(clamp_t(ds[qb * 64 * NF], T) >> 6, nkb - 1);
+        ws_first = __builtin_amdgcn_readfirstlane(clamp_t(ds[q0], T));
+        ws_last = __builtin_amdgcn_readfirstlane(clamp_t(ds[q0 + 16 * NF - 1], T));
+#pragma unroll
+        for (int f = 0; f < NF; ++f) dsl[f] = clamp_t(ds[ql[f]], T) - 4 * g;       // for key row 4 g + r
+    }
     TileLd tk, tv;
-    tk.load(Kp, ld, tid);
-    tv.load(Vp, ld, tid);
+    tk.load(Kp + (long)kb0 * 64 * ld, ld, tid);
+    tv.load(Vp + (long)kb0 * 64 * ld, ld, tid);
     tk.store(smem[0][0], tid);
     tv.store(smem[0][1], tid);
     __syncthreads();
-    for (int kb = 0; kb < nkb; ++kb) {
-        const int cur = kb & 1;
+    for (int kb = kb0; kb < nkb; ++kb) {
+        const int cur = (kb - kb0) & 1;
         const bool more = kb + 1 < nkb;
         if (more) {
             tk.load(Kp + (long)(kb + 1) * 64 * ld, ld, tid);
             tv.load(Vp + (long)(kb + 1) * 64 * ld, ld, tid);
         }
         const int k0 = kb * 64;
-        if (!causal || k0 <= q0 + 16 * NF - 1) {
+        if ((!causal || k0 <= q0 + 16 * NF - 1) && (!DOC || k0 + 63 >= ws_first)) {
             const bf16_t* Ki = smem[cur][0];
             const bf16_t* Vi = smem[cur][1];
             // S^T[key][q], dP^T[key][q]: lane holds rows key = k0 + 16 ki + 4 g + r, column q = ql[f]
@@ -568,6 +659,7 @@ __global__ void __launch_bounds__(NTA) attn_bwd_dq_kernel(const bf16_t* __restri
                 }
             }
             const bool diag = causal && k0 + 63 > q0;     // wave-uniform: only these tiles need the mask
+            const bool edge = DOC && k0 < ws_last;        // wave-uniform: some query's document starts inside or after
 #pragma unroll
             for (int f = 0; f < NF; ++f)
 #pragma unroll
@@ -578,6 +670,14 @@ __global__ void __launch_bounds__(NTA) attn_bwd_dq_kernel(const bf16_t* __restri
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
                             if (k0 + 16 * ki + 4 * g + r > ql[f]) s[f][ki][r] = 0.f;
+                    }
+                    if constexpr (DOC) {
+                        if (edge) {
+                            const int lim = dsl[f] - k0;    // key k0 + 16 ki + 4 g + r is before the document
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                if (16 * ki + r < lim) s[f][ki][r] = 0.f;
+                        }
                     }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) dp[f][ki][r] = s[f][ki][r] * (dp[f][ki][r] - dq_[f]);
@@ -614,6 +714,47 @@ __global__ void __launch_bounds__(NTA) attn_bwd_dq_kernel(const bf16_t* __restri
         }
     }
 }
+// ---------------------------------------------------------------------------------------------- document bounds
+// doc_start / doc_end of one sequence per block from its tokens: token t starts a document iff t == 0 or token t - 1
+// is EOT (the EOT token belongs to the document it ends).  doc_start = prefix max of (start flag ? t : 0), doc_end =
+// suffix min of (token t is EOT ? t + 1 : T).  Thread i owns the contiguous chunk [i n, i n + n), n = ceil(T / 256):
+// chunk totals, a 256-entry scan in LDS, then the chunk again with the carry.
+__global__ void __launch_bounds__(NTA) doc_bounds_kernel(const long long* __restrict__ idx, long long eot,
+                                                         int* __restrict__ doc_start, int* __restrict__ doc_end, int T) {
+    __shared__ int pmax[NTA], smin[NTA];
+    const int tid = threadIdx.x;
+    const long long* row = idx + (long)blockIdx.x * T;
+    int* ds = doc_start + (long)blockIdx.x * T;
+    int* de = doc_end + (long)blockIdx.x * T;
+    const int n = (T + NTA - 1) / NTA;
+    const int t0 = min(tid * n, T), t1 = min(t0 + n, T);
+    int mx = 0, mn = T;
+    for (int t = t0; t < t1; ++t) {
+        if (t > 0 && row[t - 1] == eot) mx = t;
+        if (row[t] == eot) mn = min(mn, t + 1);
+    }
+    pmax[tid] = mx;
+    smin[tid] = mn;
+    __syncthreads();
+    for (int d = 1; d < NTA; d <<= 1) {
+        const int a = tid >= d ? pmax[tid - d] : 0;
+        const int e = tid + d < NTA ? smin[tid + d] : T;
+        __syncthreads();
+        pmax[tid] = max(pmax[tid], a);
+        smin[tid] = min(smin[tid], e);
+        __syncthreads();
+    }
+    int s = tid > 0 ? pmax[tid - 1] : 0;
+    for (int t = t0; t < t1; ++t) {
+        if (t > 0 && row[t - 1] == eot) s = t;
+        ds[t] = s;
+    }
+    int e = tid + 1 < NTA ? smin[tid + 1] : T;
+    for (int t = t1 - 1; t >= t0; --t) {
+        if (row[t] == eot) e = t + 1;
+        de[t] = e;
+    }
+}
 }  // namespace
 
 static dim3 attn_grid(int ntile, int H, int B) {
@@ -624,22 +765,65 @@ static dim3 attn_grid(int ntile, int H, int B) {
 #endif
 }
 
+template <bool DOC>
+static void launch_fwd(const bf16_t* qkv, bf16_t* out, float* lse2, int B, int T, int H, float scale,
+                       typename MaskSel<DOC>::type mk, hipStream_t st) {
+    hipLaunchKernelGGL(attn_fwd_kernel<DOC>, attn_grid(T / 128, H, B), dim3(NTA), 0, st, qkv, out, lse2, T, H, scale, mk);
+}
+
 // qkv [B*T][3*H*64] bf16 -> out [B*T][H*64] bf16, lse2 [B][H][T] fp32.  T % 128 == 0.
 PDNN_API int pdnn_flash_attn_fwd(const bf16_t* qkv, bf16_t* out, float* lse2, int B, int T, int H, float scale,
                                  int causal, hipStream_t st) {
     if (B < 1 || T < 1 || H < 1 || T % 128 || !qkv || !out || !lse2) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(attn_fwd_kernel, attn_grid(T / 128, H, B), dim3(NTA), 0, st, qkv, out, lse2, T, H, scale, causal);
+    launch_fwd<false>(qkv, out, lse2, B, T, H, scale, causal, st);
     PDNN_LAUNCH_RET;
 }
 
+// the same under the packed-document mask: doc_start, doc_end int32 [B][T] (pdnn_doc_bounds)
+PDNN_API int pdnn_flash_attn_doc_fwd(const bf16_t* qkv, bf16_t* out, float* lse2, int B, int T, int H, float scale,
+                                     const int* doc_start, const int* doc_end, hipStream_t st) {
+    if (B < 1 || T < 1 || H < 1 || T % 128 || !qkv || !out || !lse2 || !doc_start || !doc_end)
+        return (int)hipErrorInvalidValue;
+    launch_fwd<true>(qkv, out, lse2, B, T, H, scale, DocArg{doc_start, doc_end}, st);
+    PDNN_LAUNCH_RET;
+}
+
+// DOC at NF = 2 needs no scratch either (profiles/attention_doc_mask.txt), so attn_bwd_wide routes it like the plain one
+template <bool DOC>
 static void launch_dkdv(const bf16_t* qkv, const bf16_t* dO, const float* lse2, const float* delta, bf16_t* dqkv, int B,
-                        int T, int H, float scale, int causal, hipStream_t st) {
+                        int T, int H, float scale, typename MaskSel<DOC>::type mk, hipStream_t st) {
     if (pg::tune().attn_bwd_wide & 2)
-        hipLaunchKernelGGL(attn_bwd_dkdv_kernel<2>, attn_grid(T / 128, H, B), dim3(NTA), 0, st, qkv, dO, lse2, delta,
-                           dqkv, T, H, scale, causal);
+        hipLaunchKernelGGL((attn_bwd_dkdv_kernel<2, DOC>), attn_grid(T / 128, H, B), dim3(NTA), 0, st, qkv, dO, lse2,
+                           delta, dqkv, T, H, scale, mk);
     else
-        hipLaunchKernelGGL(attn_bwd_dkdv_kernel<1>, attn_grid(T / 64, H, B), dim3(NTA), 0, st, qkv, dO, lse2, delta,
-                           dqkv, T, H, scale, causal);
+        hipLaunchKernelGGL((attn_bwd_dkdv_kernel<1, DOC>), attn_grid(T / 64, H, B), dim3(NTA), 0, st, qkv, dO, lse2,
+                           delta, dqkv, T, H, scale, mk);
+}
+
+template <bool DELTA, bool DOC>
+static void launch_dq(const bf16_t* qkv, const bf16_t* out, const bf16_t* dO, const float* lse2, float* delta,
+                      bf16_t* dqkv, int B, int T, int H, float scale, typename MaskSel<DOC>::type mk, hipStream_t st) {
+    if (pg::tune().attn_bwd_wide & 1)
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<DELTA, 2, DOC>), attn_grid(T / 128, H, B), dim3(NTA), 0, st, qkv, dO, lse2,
+                           delta, out, dqkv, T, H, scale, mk);
+    else
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<DELTA, 1, DOC>), attn_grid(T / 64, H, B), dim3(NTA), 0, st, qkv, dO, lse2,
+                           delta, out, dqkv, T, H, scale, mk);
+}
+
+template <bool DOC>
+static void launch_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dO, const float* lse2, float* delta,
+                       bf16_t* dqkv, int B, int T, int H, float scale, typename MaskSel<DOC>::type mk, hipStream_t st) {
+    if (pg::tune().attn_delta_in_dq) {       // dQ first (it writes delta), then dK / dV
+        launch_dq<true, DOC>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, mk, st);
+        launch_dkdv<DOC>(qkv, dO, lse2, delta, dqkv, B, T, H, scale, mk, st);
+        return;
+    }
+    const long n = (long)B * T * H;
+    hipLaunchKernelGGL(attn_bwd_delta_kernel, dim3((unsigned)((n + NTA - 1) / NTA)), dim3(NTA), 0, st, out, dO, delta,
+                       B * T, T, H);
+    launch_dkdv<DOC>(qkv, dO, lse2, delta, dqkv, B, T, H, scale, mk, st);
+    launch_dq<false, DOC>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, mk, st);
 }
 
 // dO [B*T][H*64], out/lse2 from the forward -> dqkv [B*T][3*H*64]; delta: fp32 [B][H][T] scratch.
@@ -648,26 +832,23 @@ PDNN_API int pdnn_flash_attn_bwd(const bf16_t* qkv, const bf16_t* out, const bf1
                                  hipStream_t st) {
     if (B < 1 || T < 1 || H < 1 || T % 128 || !qkv || !out || !dO || !lse2 || !delta || !dqkv)
         return (int)hipErrorInvalidValue;
-    const bool wq = pg::tune().attn_bwd_wide & 1;
-    if (pg::tune().attn_delta_in_dq) {       // dQ first (it writes delta), then dK / dV
-        if (wq)
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<true, 2>), attn_grid(T / 128, H, B), dim3(NTA), 0, st, qkv, dO, lse2,
-                               delta, out, dqkv, T, H, scale, causal);
-        else
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<true, 1>), attn_grid(T / 64, H, B), dim3(NTA), 0, st, qkv, dO, lse2,
-                               delta, out, dqkv, T, H, scale, causal);
-        launch_dkdv(qkv, dO, lse2, delta, dqkv, B, T, H, scale, causal, st);
-        PDNN_LAUNCH_RET;
-    }
-    const long n = (long)B * T * H;
-    hipLaunchKernelGGL(attn_bwd_delta_kernel, dim3((unsigned)((n + NTA - 1) / NTA)), dim3(NTA), 0, st, out, dO, delta,
-                       B * T, T, H);
-    launch_dkdv(qkv, dO, lse2, delta, dqkv, B, T, H, scale, causal, st);
-    if (wq)
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<false, 2>), attn_grid(T / 128, H, B), dim3(NTA), 0, st, qkv, dO, lse2, delta,
-                           out, dqkv, T, H, scale, causal);
-    else
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<false, 1>), attn_grid(T / 64, H, B), dim3(NTA), 0, st, qkv, dO, lse2, delta,
-                           out, dqkv, T, H, scale, causal);
+    launch_bwd<false>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, causal, st);
+    PDNN_LAUNCH_RET;
+}
+
+PDNN_API int pdnn_flash_attn_doc_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dO, const float* lse2,
+                                     float* delta, bf16_t* dqkv, int B, int T, int H, float scale, const int* doc_start,
+                                     const int* doc_end, hipStream_t st) {
+    if (B < 1 || T < 1 || H < 1 || T % 128 || !qkv || !out || !dO || !lse2 || !delta || !dqkv || !doc_start || !doc_end)
+        return (int)hipErrorInvalidValue;
+    launch_bwd<true>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, DocArg{doc_start, doc_end}, st);
+    PDNN_LAUNCH_RET;
+}
+
+// idx int64 [B][T] -> doc_start, doc_end int32 [B][T]; one block per sequence, no host read-back (capturable)
+PDNN_API int pdnn_doc_bounds(const long long* idx, long long eot, int* doc_start, int* doc_end, int B, int T,
+                             hipStream_t st) {
+    if (B < 1 || T < 1 || !idx || !doc_start || !doc_end) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(doc_bounds_kernel, dim3(B), dim3(NTA), 0, st, idx, eot, doc_start, doc_end, T);
     PDNN_LAUNCH_RET;
 }

@@ -62,6 +62,9 @@ def add_fit_args(p: argparse.ArgumentParser):
                         "kernels (0 = off; evaluation keeps the plain loss)")
     p.add_argument("--z-loss", type=float, default=0.0, metavar="Z",
                    help="training loss: + Z * logsumexp(logits)^2 per sample (PaLM's auxiliary loss; 0 = off)")
+    p.add_argument("--doc-mask-eot", type=int, default=None, metavar="ID",
+                   help="GPT-2: rows are packed documents, each ended by token ID; attention stays inside the "
+                        "document (GPT2Config.doc_mask_eot; synthetic token data places ID as its end-of-text)")
     p.add_argument("--opt-overlap", action="store_true",
                    help="DDP: apply each bucket's optimizer update right after its all-reduce, beside the rest of "
                         "the backward (DistributedDataParallel.overlap_optimizer); not with --grad-clip")
@@ -130,6 +133,13 @@ def parse_args(argv=None):
         raise SystemExit("--label-smoothing must be in [0, 1] (0 = off)")
     if not 0.0 <= args.z_loss < float("inf"):
         raise SystemExit("--z-loss must be finite and >= 0 (0 = off)")
+    if args.doc_mask_eot is not None:
+        from .models import _ALIASES
+        if not _ALIASES.get(args.network, args.network).lower().startswith("gpt2"):
+            raise SystemExit(f"--doc-mask-eot masks attention across packed documents: network {args.network} has no "
+                             f"attention (GPT-2 only)")
+        if args.doc_mask_eot < 0:
+            raise SystemExit("--doc-mask-eot must be a token id (>= 0)")
     if args.grad_clip and args.opt_overlap:
         raise SystemExit("--grad-clip cannot be combined with --opt-overlap: the overlapped optimizer updates each "
                          "bucket during the backward, before the gradient's global norm exists")
@@ -210,6 +220,11 @@ def main(argv=None):
             model.config.fp8 = True
         else:
             raise SystemExit(f"--dtype fp8: network {args.network} has no fp8 path (ResNet Bottlenecks, GPT-2)")
+    if args.doc_mask_eot is not None:
+        if not 0 <= args.doc_mask_eot < model.config.vocab_size:
+            raise SystemExit(f"--doc-mask-eot {args.doc_mask_eot} is not a token of {args.network} (vocabulary "
+                             f"{model.config.vocab_size})")
+        model.config.doc_mask_eot = args.doc_mask_eot
     xdt = torch.bfloat16 if (dev.type == "cuda" and args.dtype in ("bf16", "fp8")) else torch.float32
     # the training loss; evaluation (evaluate below, Trainer.evaluate, evaluator.py) keeps the plain cross-entropy
     train_loss = OF.cross_entropy

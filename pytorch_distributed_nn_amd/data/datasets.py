@@ -1,6 +1,7 @@
 """Datasets, readers and the prefetching loader (see package docstring)."""
 from __future__ import annotations
 
+import math
 import os
 import queue
 import threading
@@ -157,13 +158,38 @@ class SyntheticDataset:
 
 
 class SyntheticTokens:
-    """Random token sequences for language models: (input ids, next-token targets)."""
+    """Random token sequences for language models: (input ids, next-token targets).
 
-    def __init__(self, vocab, seq_len, batch_size, device="cpu", n_batches=2, seed=0):
+    ``eot``: packed documents: every row is a run of documents, each ended by the token ``eot``, at seeded geometric
+    gaps of mean ``mean_doc_len`` (default seq_len // 4); no other token equals ``eot``."""
+
+    def __init__(self, vocab, seq_len, batch_size, device="cpu", n_batches=2, seed=0, eot=None, mean_doc_len=None):
         g = torch.Generator(device="cpu").manual_seed(seed)
+        if eot is None and mean_doc_len is not None:
+            raise ValueError("SyntheticTokens: mean_doc_len needs eot")
+        if eot is not None:
+            if not 0 <= eot < vocab or vocab < 2:
+                raise ValueError(f"SyntheticTokens: eot {eot} is not a token of a vocabulary of {vocab}")
+            mean_doc_len = float(mean_doc_len if mean_doc_len is not None else max(2, seq_len // 4))
+            if not mean_doc_len >= 1.0:
+                raise ValueError(f"SyntheticTokens: mean_doc_len {mean_doc_len} must be >= 1")
         self.batches = []
         for _ in range(n_batches):
-            t = torch.randint(0, vocab, (batch_size, seq_len + 1), generator=g).to(device)
+            if eot is None:
+                t = torch.randint(0, vocab, (batch_size, seq_len + 1), generator=g)
+            else:
+                t = torch.randint(0, vocab - 1, (batch_size, seq_len + 1), generator=g)
+                t = t + (t >= eot).long()                               # every id but eot
+                # document lengths (the EOT included) ~ 1 + Geometric(1 / mean_doc_len): EOT at the cumulated ends
+                u = torch.rand(batch_size, seq_len + 1, generator=g, dtype=torch.float64)
+                if mean_doc_len > 1.0:
+                    lens = 1 + torch.floor(torch.log1p(-u) / math.log1p(-1.0 / mean_doc_len)).long()
+                else:
+                    lens = torch.ones_like(t)
+                ends = lens.cumsum(1) - 1
+                for b in range(batch_size):
+                    t[b, ends[b][ends[b] <= seq_len]] = eot
+            t = t.to(device)
             self.batches.append((t[:, :-1].contiguous(), t[:, 1:].contiguous()))
         self._i = 0
 

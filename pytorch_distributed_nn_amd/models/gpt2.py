@@ -12,6 +12,11 @@ GPU path: ``ops.transformer`` fused Functions (one autograd node per block); CPU
 fp32 (tests, and the numerics reference of the GPU path).  ``forward(idx, targets)`` returns the mean
 next-token cross-entropy when targets are given (the fused head never materialises fp32 logits),
 otherwise the logits.
+
+Packed documents (``GPT2Config.doc_mask_eot`` or ``forward(..., doc_bounds=)``): rows that concatenate several
+documents, each ended by an end-of-text token, attend causally inside their own document only (the DOC kernels of
+``csrc/kernels/attention.hip``; on the CPU an equivalent boolean mask for SDPA).  The learned absolute positions are
+unchanged: position t of the row, not reset at a document start.
 """
 from __future__ import annotations
 
@@ -40,6 +45,9 @@ class GPT2Config:
     # training loss only (grad mode on); an evaluation forward returns the plain cross-entropy
     label_smoothing: float = 0.0   # eps: target = (1 - eps) onehot + eps / vocab_size
     z_loss: float = 0.0            # z: + z * logsumexp^2 per token (PaLM)
+    # packed documents: the id of the end-of-text token that ends (and belongs to) each document of a row; attention
+    # then stays inside the document.  None = plain causal attention over the whole row.  Positions are not reset.
+    doc_mask_eot: int | None = None
 
 
 CONFIGS = {
@@ -58,11 +66,14 @@ class Attention(nn.Module):
         self.c_attn = nn.Linear(c.n_embd, 3 * c.n_embd)
         self.c_proj = nn.Linear(c.n_embd, c.n_embd)
 
-    def forward(self, x):
+    def forward(self, x, mask=None):
         B, T, D = x.shape
         q, k, v = self.c_attn(x).split(D, dim=2)
         q, k, v = (t.view(B, T, self.n_head, D // self.n_head).transpose(1, 2) for t in (q, k, v))
-        y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
+        if mask is not None:        # bool [B][1][T][T], True = visible (causal and inside the document)
+            y = F.scaled_dot_product_attention(q, k, v, attn_mask=mask)
+        else:
+            y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
         return self.c_proj(y.transpose(1, 2).reshape(B, T, D))
 
 
@@ -84,8 +95,8 @@ class Block(nn.Module):
         self.ln_2 = nn.LayerNorm(c.n_embd, eps=c.eps)
         self.mlp = MLP(c)
 
-    def forward(self, x):
-        x = x + self.attn(self.ln_1(x))
+    def forward(self, x, mask=None):
+        x = x + self.attn(self.ln_1(x), mask)
         return x + self.mlp(self.ln_2(x))
 
     def fp8_metas(self, device):
@@ -165,12 +176,32 @@ class GPT2(nn.Module):
             self.__dict__["_pdnn_t_ws"] = ws
         return ws
 
-    def forward(self, idx, targets=None):
+    def _doc_bounds(self, idx, doc_bounds):
+        """(doc_start, doc_end) int32 [B][T] on idx's device, or None: explicit bounds win over config.doc_mask_eot"""
+        if doc_bounds is not None:
+            ds, de = doc_bounds
+            if ds.shape != idx.shape or de.shape != idx.shape:
+                raise ValueError(f"doc_bounds: expected two [B][T] = {tuple(idx.shape)} tensors, got {tuple(ds.shape)}, "
+                                 f"{tuple(de.shape)}")
+            return tuple(t.to(device=idx.device, dtype=torch.int32).contiguous() for t in (ds, de))
+        eot = self.config.doc_mask_eot
+        if eot is None:
+            return None
+        if idx.is_cuda:             # one small kernel per forward, no host read-back: the step stays capturable
+            from ..ops import kernels as K
+            return K.doc_bounds(idx.long().contiguous(), int(eot))
+        return TX.doc_bounds_reference(idx, int(eot))
+
+    def forward(self, idx, targets=None, doc_bounds=None):
+        """``doc_bounds``: optional (doc_start, doc_end), integer [B][T], for callers that pack themselves (first token
+        of t's document, one past its last); otherwise config.doc_mask_eot, when set, derives them from ``idx`` once
+        per forward on the device, for every block."""
         B, T = idx.shape
         c = self.config
         assert T <= c.block_size, f"sequence length {T} > block size {c.block_size}"
+        doc = self._doc_bounds(idx, doc_bounds)
         if not idx.is_cuda:
-            return self._forward_reference(idx, targets)
+            return self._forward_reference(idx, targets, doc)
         tr = self.transformer
         wte, wpe = tr.wte.weight, tr.wpe.weight
         pf = tuning.get("wt_prefetch")
@@ -192,7 +223,7 @@ class GPT2(nn.Module):
         for blk in tr.h:
             params, shadows = blk.fused_params()
             metas = blk.fp8_metas(x.device) if c.fp8 else None
-            x = TX.GPT2BlockFn.apply(x, (B, T, c.n_head, c.eps, metas), shadows, *params)
+            x = TX.GPT2BlockFn.apply(x, (B, T, c.n_head, c.eps, metas, doc), shadows, *params)
         if targets is None:
             xf = TX.layer_norm(x, tr.ln_f.weight, tr.ln_f.bias, c.eps)
             return OF.linear(xf, wte).view(B, T, -1)
@@ -201,8 +232,9 @@ class GPT2(nn.Module):
                                      tr.ln_f.bias, wte, hd, ddp is not None, train,
                                      c.label_smoothing if train else 0.0, c.z_loss if train else 0.0)
 
-    def _forward_reference(self, idx, targets=None):
+    def _forward_reference(self, idx, targets=None, doc=None):
         B, T = idx.shape
+        mask = TX.doc_visible(doc[0]).unsqueeze(1) if doc is not None else None
         tr = self.transformer
         pos = torch.arange(T, device=idx.device)
         ddp = self._row_tail() if targets is not None and torch.is_grad_enabled() else None
@@ -211,7 +243,7 @@ class GPT2(nn.Module):
         else:
             x = tr.wte(idx) + tr.wpe(pos)
         for blk in tr.h:
-            x = blk(x)
+            x = blk(x, mask)
         logits = self.lm_head(tr.ln_f(x))
         if targets is None:
             return logits

@@ -141,6 +141,9 @@ _SIGS = {
     "pdnn_attn_softmax_bwd": [P, L, P, L, P, L, I, I, F, I, P],
     "pdnn_flash_attn_fwd": [P, P, P, I, I, I, F, I, P],
     "pdnn_flash_attn_bwd": [P, P, P, P, P, P, I, I, I, F, I, P],
+    "pdnn_flash_attn_doc_fwd": [P, P, P, I, I, I, F, P, P, P],
+    "pdnn_flash_attn_doc_bwd": [P, P, P, P, P, P, I, I, I, F, P, P, P],
+    "pdnn_doc_bounds": [P, ctypes.c_longlong, P, P, I, I, P],
     "pdnn_embedding_fwd": [P, P, P, P, I, I, I, P],
     "pdnn_embedding_bwd": [P, P, P, P, I, I, I, P],
     "pdnn_embedding_bwd_scaled": [P, P, P, P, I, I, I, F, P],

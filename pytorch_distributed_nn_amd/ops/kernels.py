@@ -1434,6 +1434,58 @@ def flash_attn_bwd(qkv, out, dout, lse2, B, T, H, scale, causal=True):
     return dqkv
 
 
+def doc_bounds(idx, eot):
+    """Packed-document bounds of token ids idx int64 [B][T] on the device, no host read-back: (doc_start, doc_end) int32
+    [B][T], the first token of t's document and one past its last.  A document ends with (and includes) its ``eot``."""
+    _chk(idx.dtype == torch.int64 and idx.is_cuda and idx.dim() == 2 and idx.is_contiguous(),
+         f"doc_bounds: idx must be contiguous CUDA int64 [B][T], got {idx.dtype} {tuple(idx.shape)} {idx.device}")
+    B, T = idx.shape
+    _chk(B >= 1 and T >= 1, f"doc_bounds: idx {tuple(idx.shape)}")
+    _chk(isinstance(eot, int) and not isinstance(eot, bool), f"doc_bounds: eot must be an int, got {eot!r}")
+    ds = torch.empty(B, T, device=idx.device, dtype=torch.int32)
+    de = torch.empty(B, T, device=idx.device, dtype=torch.int32)
+    call("pdnn_doc_bounds", ptr(idx), eot, ptr(ds), ptr(de), B, T, stream())
+    return ds, de
+
+
+def _doc_chk(name, doc_start, doc_end, B, T, dev):
+    for t, what in ((doc_start, "doc_start"), (doc_end, "doc_end")):
+        _chk(torch.is_tensor(t) and t.dtype == torch.int32 and t.shape == (B, T) and t.is_contiguous() and t.device == dev,
+             f"{name}: {what} must be contiguous int32 [B][T] on {dev}")
+
+
+def flash_attn_doc_fwd(qkv, doc_start, doc_end, B, T, H, scale):
+    """flash_attn_fwd under the causal packed-document mask: query q of sequence b sees key k iff
+    doc_start[b][q] <= k <= q (bounds as from :func:`doc_bounds`)."""
+    _bf16_c(qkv, "flash_attn_doc.qkv")
+    _chk(B >= 1 and T >= 1 and H >= 1 and qkv.shape == (B * T, 3 * H * 64) and T % 128 == 0,
+         f"flash_attn_doc: qkv {tuple(qkv.shape)} B={B} T={T} H={H}")
+    _doc_chk("flash_attn_doc", doc_start, doc_end, B, T, qkv.device)
+    out = torch.empty(B * T, H * 64, device=qkv.device, dtype=BF16)
+    lse2 = torch.empty(B, H, T, device=qkv.device, dtype=F32)
+    call("pdnn_flash_attn_doc_fwd", ptr(qkv), ptr(out), ptr(lse2), B, T, H, float(scale), ptr(doc_start), ptr(doc_end),
+         stream())
+    return out, lse2
+
+
+def flash_attn_doc_bwd(qkv, out, dout, lse2, doc_start, doc_end, B, T, H, scale):
+    _bf16_c(qkv, "flash_attn_doc_bwd.qkv")
+    _chk(B >= 1 and T >= 1 and H >= 1 and qkv.shape == (B * T, 3 * H * 64) and T % 128 == 0,
+         f"flash_attn_doc_bwd: qkv {tuple(qkv.shape)} B={B} T={T} H={H}")
+    dout = dout.contiguous()
+    _chk(out.dtype == BF16 and out.shape == (B * T, H * 64) and out.is_contiguous(),
+         "flash_attn_doc_bwd: out must be contiguous bf16 [B*T][H*64]")
+    _chk(dout.dtype == BF16 and dout.shape == out.shape, "flash_attn_doc_bwd: dout must be bf16 of out's shape")
+    _chk(lse2.dtype == F32 and lse2.shape == (B, H, T) and lse2.is_contiguous(),
+         "flash_attn_doc_bwd: lse2 must be contiguous fp32 [B][H][T]")
+    _doc_chk("flash_attn_doc_bwd", doc_start, doc_end, B, T, qkv.device)
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty(B, H, T, device=qkv.device, dtype=F32)
+    call("pdnn_flash_attn_doc_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse2), ptr(delta), ptr(dqkv), B, T, H,
+         float(scale), ptr(doc_start), ptr(doc_end), stream())
+    return dqkv
+
+
 def embedding_fwd(idx, wte, wpe, T):
     R = idx.numel()
     D = wte.shape[1]

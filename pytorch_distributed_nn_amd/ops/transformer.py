@@ -96,12 +96,39 @@ def use_flash(T, D, H):
     return D // H == 64 and T % 128 == 0
 
 
-def attention_reference(qkv, B, T, H, causal=True):
-    """fp32 PyTorch reference of :func:`attention_fwd` (tests, CPU path)."""
+def attention_reference(qkv, B, T, H, causal=True, mask=None):
+    """fp32 PyTorch reference of :func:`attention_fwd` (tests, CPU path).  ``mask``: optional bool [B][T][T] (or
+    broadcastable to [B][H][T][T]), True where the query (row) sees the key (column); it replaces ``causal``
+    (:func:`doc_visible` builds the causal packed-document one)."""
     D = qkv.shape[1] // 3
     q, k, v = qkv.float().view(B, T, 3, H, D // H).permute(2, 0, 3, 1, 4)
-    y = F.scaled_dot_product_attention(q, k, v, is_causal=causal)
+    if mask is not None:
+        m = mask if mask.dim() == 4 else mask.unsqueeze(1)
+        y = F.scaled_dot_product_attention(q, k, v, attn_mask=m)
+    else:
+        y = F.scaled_dot_product_attention(q, k, v, is_causal=causal)
     return y.transpose(1, 2).reshape(B * T, D)
+
+
+def doc_bounds_reference(idx, eot):
+    """PyTorch form of kernels.doc_bounds (any device): idx [B][T] -> (doc_start, doc_end) int32 [B][T].  Token t starts
+    a document iff t == 0 or token t - 1 is ``eot``: the EOT token belongs to the document it ends."""
+    B, T = idx.shape
+    t = torch.arange(T, device=idx.device).expand(B, T)
+    is_eot = idx == eot
+    starts = torch.zeros_like(is_eot)
+    starts[:, 1:] = is_eot[:, :-1]
+    ds = torch.where(starts, t, torch.zeros_like(t)).cummax(1).values
+    ends = torch.where(is_eot, t + 1, torch.full_like(t, T))
+    de = ends.flip(1).cummin(1).values.flip(1)
+    return ds.to(torch.int32).contiguous(), de.to(torch.int32).contiguous()
+
+
+def doc_visible(doc_start):
+    """bool [B][T][T] of the causal packed-document mask: query q sees key k iff doc_start[b][q] <= k <= q"""
+    B, T = doc_start.shape
+    i = torch.arange(T, device=doc_start.device)
+    return (i[None, None, :] <= i[None, :, None]) & (i[None, None, :] >= doc_start.long()[:, :, None])
 
 
 # ------------------------------------------------------------------------------------------------
@@ -276,6 +303,7 @@ class GPT2BlockFn(torch.autograd.Function):
     def forward(ctx, x, conf, shadows, *params):
         B, T, H, eps = conf[:4]
         metas = conf[4] if len(conf) > 4 else None
+        doc = conf[5] if len(conf) > 5 else None        # (doc_start, doc_end) int32 [B][T]: packed-document mask
         ln1w, ln1b, _, attn_b, _, proj_b, ln2w, ln2b, _, fc_b, _, fc2_b = params
         wqkv, wproj, wfc, wfc2 = shadows
         if metas is not None:
@@ -290,7 +318,13 @@ class GPT2BlockFn(torch.autograd.Function):
         qkv = lin(ln1, 2, wqkv, bias=attn_b)
         D = x.shape[1]
         flash = use_flash(T, D, H)
-        if flash:
+        if doc is not None and not flash:
+            raise ValueError(f"packed-document attention needs the fused kernels (head dim 64, T % 128 == 0); got head "
+                             f"dim {D // H}, T = {T}: the unfused attention chain has no document mask")
+        if doc is not None:
+            y, P = K.flash_attn_doc_fwd(qkv, doc[0], doc[1], B, T, H, 1.0 / math.sqrt(D // H))
+            S = None
+        elif flash:
             y, P = K.flash_attn_fwd(qkv, B, T, H, 1.0 / math.sqrt(D // H))     # P := lse2
             S = None
         else:
@@ -328,7 +362,10 @@ class GPT2BlockFn(torch.autograd.Function):
         # attention
         dy = BL.linear_dgrad(dx1, wproj, p=Pm[4])
         dproj_w, dproj_b = sink.linear(Pm[4], Pm[5], dx1, y)
-        if ctx.flash:
+        doc = ctx.conf[5] if len(ctx.conf) > 5 else None
+        if doc is not None:
+            dqkv = K.flash_attn_doc_bwd(qkv, y, dy, P, doc[0], doc[1], B, T, H, 1.0 / math.sqrt(x.shape[1] // H))
+        elif ctx.flash:
             dqkv = K.flash_attn_bwd(qkv, y, dy, P, B, T, H, 1.0 / math.sqrt(x.shape[1] // H))
         else:
             dqkv = attention_bwd(dy, qkv, P, B, T, H, dS_buf=ctx.S)

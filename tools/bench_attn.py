@@ -1,7 +1,12 @@
 """Time the fused attention kernels (attention.hip) alone at GPT-2 shapes vs torch SDPA (reference point).
 
     python tools/bench_attn.py            # one JSON line per config
+    python tools/bench_attn.py --doc-len 256 [--rounds 7]
+        packed documents of N tokens at B8 / T1024 / H12: the DOC kernels and the plain causal ones alternate in one
+        process, ROUNDS times; medians, the plain kernel's own spread across the rounds, and the ratio beside the work
+        ratio sum(len^2) / T^2
 """
+import argparse
 import json
 import math
 import os
@@ -27,7 +32,46 @@ def timeit(fn, iters=20):
     return s.elapsed_time(e) / iters * 1e3       # us
 
 
+def doc_main(doc_len, rounds):
+    B, T, H = 8, 1024, 12
+    sc = 1 / math.sqrt(64)
+    qkv = (torch.randn(B * T, 3 * H * 64, device="cuda") * 0.5).to(torch.bfloat16)
+    t = torch.arange(T, device="cuda", dtype=torch.int32)
+    ds = (t // doc_len * doc_len).expand(B, T).contiguous()
+    de = (ds + doc_len).clamp_max(T).contiguous()
+    out, lse = K.flash_attn_fwd(qkv, B, T, H, sc, True)
+    outd, lsed = K.flash_attn_doc_fwd(qkv, ds, de, B, T, H, sc)
+    do = torch.randn_like(out)
+    fns = {"plain_fwd": lambda: K.flash_attn_fwd(qkv, B, T, H, sc, True),
+           "doc_fwd": lambda: K.flash_attn_doc_fwd(qkv, ds, de, B, T, H, sc),
+           "plain_bwd": lambda: K.flash_attn_bwd(qkv, out, do, lse, B, T, H, sc, True),
+           "doc_bwd": lambda: K.flash_attn_doc_bwd(qkv, outd, do, lsed, ds, de, B, T, H, sc)}
+    times = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            times[k].append(timeit(fn, iters=50))
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    lens = [min(doc_len, T - s) for s in range(0, T, doc_len)]
+    r = {"B": B, "T": T, "H": H, "doc_len": doc_len, "rounds": rounds, "work_ratio": sum(n * n for n in lens) / (T * T)}
+    for d in ("fwd", "bwd"):
+        p, q = times["plain_" + d], times["doc_" + d]
+        r[d] = {"plain_us": med["plain_" + d], "doc_us": med["doc_" + d], "ratio": med["doc_" + d] / med["plain_" + d],
+                "plain_min_max_us": [min(p), max(p)], "doc_min_max_us": [min(q), max(q)],
+                "plain_spread": (max(p) - min(p)) / med["plain_" + d]}
+    rnd = lambda v: round(v, 3) if isinstance(v, float) else ([rnd(x) for x in v] if isinstance(v, list) else  # noqa: E731
+                                                              ({k: rnd(x) for k, x in v.items()} if isinstance(v, dict) else v))
+    print(json.dumps(rnd(r)), flush=True)
+
+
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--doc-len", type=int, default=0, help="packed documents of N tokens vs the plain causal kernels")
+    ap.add_argument("--rounds", type=int, default=7)
+    a = ap.parse_args()
+    if a.doc_len:
+        if a.doc_len < 1:
+            raise SystemExit("--doc-len must be >= 1")
+        return doc_main(a.doc_len, a.rounds)
     for B, T, H, causal in [(8, 1024, 12, True), (8, 1024, 12, False), (2, 4096, 12, True), (32, 1024, 12, True)]:
         D = H * 64
         qkv = (torch.randn(B * T, 3 * D, device="cuda") * 0.5).to(torch.bfloat16)
