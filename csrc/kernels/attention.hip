@@ -39,6 +39,7 @@
 // the order of decreasing work (a late query tile may hold one short document); a work-sorted order is left for a
 // measured follow-up.
 #include "common.h"
+#include "dropout_rng.h"
 #include "tuning.h"
 
 // Block order over (query or key tile, head, sequence): 0 = 3-D grid, heavy tiles first inside each (head, sequence);
@@ -72,10 +73,37 @@ struct DocArg {
     const int* start;           // doc_start [B][T]
     const int* end;             // doc_end [B][T]
 };
-template <bool DOC> struct MaskSel { typedef int type; };
-template <> struct MaskSel<true> { typedef DocArg type; };
+// DROP: the same with the dropout argument behind it, so the plain and DOC kernels keep the signature they had
+struct CausalDrop {
+    int causal;
+    pdrop::Arg drop;
+};
+struct DocDrop {
+    DocArg doc;
+    pdrop::Arg drop;
+};
+template <bool DOC, bool DROP = false> struct MaskSel { typedef int type; };
+template <> struct MaskSel<true, false> { typedef DocArg type; };
+template <> struct MaskSel<false, true> { typedef CausalDrop type; };
+template <> struct MaskSel<true, true> { typedef DocDrop type; };
 __device__ __forceinline__ int mask_causal(int causal) { return causal; }
 __device__ __forceinline__ int mask_causal(const DocArg&) { return 1; }
+__device__ __forceinline__ int mask_causal(const CausalDrop& m) { return m.causal; }
+__device__ __forceinline__ int mask_causal(const DocDrop&) { return 1; }
+__device__ __forceinline__ const DocArg& mask_doc(const DocArg& m) { return m; }
+__device__ __forceinline__ const DocArg& mask_doc(const DocDrop& m) { return m.doc; }
+// this block's dropout stream: key of (state, site, b * H + h), and x0 = k0 + q * (T / 4) of a query row
+struct DropCtx {
+    uint32_t k0, k1, thr;
+    float scale;
+};
+template <typename M>
+__device__ __forceinline__ DropCtx drop_ctx(const M& m, int b, int h, int H) {
+    const pdrop::Key k = pdrop::stream_key(m.drop.state, m.drop.site, (uint32_t)(b * H + h));
+    return DropCtx{k.k0, k.k1, m.drop.thr, m.drop.scale};
+}
+__device__ __forceinline__ DropCtx drop_ctx(int, int, int, int) { return DropCtx{0u, 0u, 0u, 1.f}; }
+__device__ __forceinline__ DropCtx drop_ctx(const DocArg&, int, int, int) { return DropCtx{0u, 0u, 0u, 1.f}; }
 __device__ __forceinline__ int clamp_t(int v, int T) { return min(max(v, 0), T); }
 constexpr float RESC = 8.f;     // forward lazy-rescale threshold (log2 units)
 constexpr float LOG2E = 1.4426950408889634f;
@@ -165,10 +193,12 @@ __device__ __forceinline__ float rmax4(float v) { return pl32(pl16(v, true), tru
 __device__ __forceinline__ float rsum4(float v) { return pl32(pl16(v, false), false); }
 
 // ---------------------------------------------------------------------------------------------- forward
-template <bool DOC>
+// DROP: l and lse2 come from the undropped P (the softmax is unchanged); only the P packed into the P V operand is
+// masked, and 1 / (1 - p) rides on the final 1 / l
+template <bool DOC, bool DROP>
 __global__ void __launch_bounds__(NTA) attn_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                        float* __restrict__ lse2, int T, int H, float scale,
-                                                       typename MaskSel<DOC>::type mk) {
+                                                       typename MaskSel<DOC, DROP>::type mk) {
     const int causal = mask_causal(mk);
     __shared__ __attribute__((aligned(16))) bf16_t smem[2][2][64 * HD];     // [buf][K|V]
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4;
@@ -206,12 +236,19 @@ __global__ void __launch_bounds__(NTA) attn_fwd_kernel(const bf16_t* __restrict_
     // DOC: first key tile of the block, doc_start of the wave's first / last query (wave-uniform), of this lane's queries
     int kb0 = 0, ws_first = 0, ws_last = 0, dsl[2] = {0, 0};
     if constexpr (DOC) {
-        const int* ds = mk.start + (long)b * T;
+        const int* ds = mask_doc(mk).start + (long)b * T;
         kb0 = min(clamp_t(ds[qb * 128], T) >> 6, nkb - 1);
         ws_first = __builtin_amdgcn_readfirstlane(clamp_t(ds[q0], T));
         ws_last = __builtin_amdgcn_readfirstlane(clamp_t(ds[q0 + 31], T));
 #pragma unroll
         for (int f = 0; f < 2; ++f) dsl[f] = clamp_t(ds[q0 + 16 * f + (lane & 15)], T) - 4 * g;    // for key row 4 g + r
+    }
+    // DROP: x of the word of (this lane's query of fragment f, key granule g of tile 0): + (k0 >> 2) + 4 kf per word
+    const DropCtx dc = drop_ctx(mk, b, h, H);
+    uint32_t dx0[2] = {0u, 0u};
+    if constexpr (DROP) {
+#pragma unroll
+        for (int f = 0; f < 2; ++f) dx0[f] = dc.k0 + (uint32_t)(q0 + 16 * f + (lane & 15)) * (uint32_t)(T >> 2) + g;
     }
     // K/V tiles: prefetch distance 2 (two register stages + two LDS buffers).  The per-tile compute of a
     // d=64 head is short, so with distance 1 every iteration waited out most of a global-load round trip
@@ -302,6 +339,15 @@ __global__ void __launch_bounds__(NTA) attn_fwd_kernel(const bf16_t* __restrict_
                     }
                 l[f] = l[f] * alpha + rs;                           // this lane's partial; rows summed at the end
                 m[f] = mn;
+                if constexpr (DROP) {                               // after the row sum: l stays the undropped one
+#pragma unroll
+                    for (int kf = 0; kf < 4; ++kf) {
+                        const uint32_t wd = pdrop::word_x(dx0[f] + (uint32_t)((k0 >> 2) + 4 * kf), dc.k1);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (!pdrop::keep(wd, r, dc.thr)) s[kf][f][r] = 0.f;
+                    }
+                }
                 if (moved) {
 #pragma unroll
                     for (int df = 0; df < 4; ++df) o[df][f] *= alpha;
@@ -335,7 +381,7 @@ __global__ void __launch_bounds__(NTA) attn_fwd_kernel(const bf16_t* __restrict_
     for (int f = 0; f < 2; ++f) {
         const int qi = q0 + 16 * f + (lane & 15);
         l[f] = rsum4(l[f]);
-        const float inv = 1.f / l[f];
+        const float inv = DROP ? dc.scale / l[f] : 1.f / l[f];
         bf16_t* op = out + ((long)b * T + qi) * D + h * HD;
 #pragma unroll
         for (int df = 0; df < 4; ++df) {
@@ -374,11 +420,12 @@ __global__ void __launch_bounds__(NTA) attn_bwd_delta_kernel(const bf16_t* __res
 
 // dK, dV for 64 NF keys per block (wave w: NF 16-key fragments from k0 = 64 NF kb + 16 NF w); loop over 64-query
 // tiles.  NF = 2 reads every Q / dO fragment out of LDS once for two key fragments (see attn_bwd_dq_kernel).
-template <int NF, bool DOC>
+// DROP: dV^T += dO^T (P o keep), scaled by 1 / (1 - p) at the end; dS = P (keep dP / (1 - p) - delta)
+template <int NF, bool DOC, bool DROP>
 __global__ void __launch_bounds__(NTA) attn_bwd_dkdv_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dO,
                                                             const float* __restrict__ lse2, const float* __restrict__ delta,
                                                             bf16_t* __restrict__ dqkv, int T, int H, float scale,
-                                                            typename MaskSel<DOC>::type mk) {
+                                                            typename MaskSel<DOC, DROP>::type mk) {
     const int causal = mask_causal(mk);
     __shared__ __attribute__((aligned(16))) bf16_t smem[2][2][64 * HD];     // [buf][Q|dO]
     // the query tile's lse2 / delta ride along with its Q / dO tile through LDS: loaded from global memory in the
@@ -419,13 +466,22 @@ __global__ void __launch_bounds__(NTA) attn_bwd_dkdv_kernel(const bf16_t* __rest
     // (wave-uniform) and of this lane's keys
     int we_first = 0, we_last = 0, del[NF];
     if constexpr (DOC) {
-        const int* de = mk.end + (long)b * T;
+        const int* de = mask_doc(mk).end + (long)b * T;
         nqb = max(min((clamp_t(de[kb * 64 * NF + 64 * NF - 1], T) + 63) >> 6, nqb), qb0 + 1);
         we_first = __builtin_amdgcn_readfirstlane(clamp_t(de[k0], T));
         we_last = __builtin_amdgcn_readfirstlane(clamp_t(de[k0 + 16 * NF - 1], T));
 #pragma unroll
         for (int f = 0; f < NF; ++f) del[f] = clamp_t(de[k0 + 16 * f + (lane & 15)], T) - 4 * g;   // for query row 4 g + r
     }
+    // DROP: this lane's keys are element (kl & 3) of granule kl >> 2; x of query 4 g of tile 0, + (qs + 16 qi + r) T / 4
+    const DropCtx dc = drop_ctx(mk, b, h, H);
+    uint32_t dx0[NF];
+    if constexpr (DROP) {
+#pragma unroll
+        for (int f = 0; f < NF; ++f)
+            dx0[f] = dc.k0 + (uint32_t)((k0 + 16 * f + (lane & 15)) >> 2) + (uint32_t)(4 * g) * (uint32_t)(T >> 2);
+    }
+    const int dj = 8 * (lane & 3);                   // key & 3 = lane & 3: the byte of the word
     // threads 0-15 move the tile's lse2, 16-31 its delta (one float4 each)
     const float* lsrc = tid < 16 ? L2 + 4 * tid : Dl + 4 * (tid - 16);
     float4 lrow = {0.f, 0.f, 0.f, 0.f};
@@ -494,8 +550,19 @@ __global__ void __launch_bounds__(NTA) attn_bwd_dkdv_kernel(const bf16_t* __rest
                                 if (16 * qi + r >= lim) s[f][qi][r] = 0.f;
                         }
                     }
+                    if constexpr (DROP) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) dp[f][qi][r] = s[f][qi][r] * (dp[f][qi][r] - da[r]);
+                        for (int r = 0; r < 4; ++r) {
+                            const uint32_t wd = pdrop::word_x(dx0[f] + (uint32_t)(qs + 16 * qi + r) * (uint32_t)(T >> 2), dc.k1);
+                            const bool kp = ((wd >> dj) & 255u) >= dc.thr;
+                            const float pr = s[f][qi][r];
+                            dp[f][qi][r] = pr * ((kp ? dp[f][qi][r] * dc.scale : 0.f) - da[r]);
+                            s[f][qi][r] = kp ? pr : 0.f;
+                        }
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) dp[f][qi][r] = s[f][qi][r] * (dp[f][qi][r] - da[r]);
+                    }
                 }
             }
 #pragma unroll
@@ -542,7 +609,7 @@ __global__ void __launch_bounds__(NTA) attn_bwd_dkdv_kernel(const bf16_t* __rest
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 a[r] = f2bf(dk[f][df][r] * scale);
-                v[r] = f2bf(dv[f][df][r]);
+                v[r] = f2bf(DROP ? dv[f][df][r] * dc.scale : dv[f][df][r]);
             }
             *reinterpret_cast<u16x4_t*>(dkp + 16 * df + 4 * g) = a;
             *reinterpret_cast<u16x4_t*>(dvp + 16 * df + 4 * g) = v;
@@ -555,12 +622,13 @@ __global__ void __launch_bounds__(NTA) attn_bwd_dkdv_kernel(const bf16_t* __rest
 // per tile came with 24 KB of LDS reads, which saturated the LDS array (256 B/clk/CU) at the MFMA rate.
 // DELTA: the block also forms delta = rowsum(dO . O) of its queries (the four 16-lane groups of a query row take
 // 16 dims each) and writes it for attn_bwd_dkdv_kernel, which then runs after it: no separate delta launch
-template <bool DELTA, int NF, bool DOC>
+// DROP: dS^T = P^T (keep dP^T / (1 - p) - delta); delta = rowsum(dO . O) already holds the dropout through O
+template <bool DELTA, int NF, bool DOC, bool DROP>
 __global__ void __launch_bounds__(NTA) attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dO,
                                                           const float* __restrict__ lse2, float* __restrict__ delta,
                                                           const bf16_t* __restrict__ o,
                                                           bf16_t* __restrict__ dqkv, int T, int H, float scale,
-                                                          typename MaskSel<DOC>::type mk) {
+                                                          typename MaskSel<DOC, DROP>::type mk) {
     const int causal = mask_causal(mk);
     __shared__ __attribute__((aligned(16))) bf16_t smem[2][2][64 * HD];     // [buf][K|V]
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4;
@@ -618,12 +686,18 @@ __global__ void __launch_bounds__(NTA) attn_bwd_dq_kernel(const bf16_t* __restri
     // DOC: as in the forward, per 16 NF-query wave
     int kb0 = 0, ws_first = 0, ws_last = 0, dsl[NF];
     if constexpr (DOC) {
-        const int* ds = mk.start + (long)b * T;
+        const int* ds = mask_doc(mk).start + (long)b * T;
         kb0 = min(clamp_t(ds[qb * 64 * NF], T) >> 6, nkb - 1);
         ws_first = __builtin_amdgcn_readfirstlane(clamp_t(ds[q0], T));
         ws_last = __builtin_amdgcn_readfirstlane(clamp_t(ds[q0 + 16 * NF - 1], T));
 #pragma unroll
         for (int f = 0; f < NF; ++f) dsl[f] = clamp_t(ds[ql[f]], T) - 4 * g;       // for key row 4 g + r
+    }
+    const DropCtx dc = drop_ctx(mk, b, h, H);        // DROP: as in the forward
+    uint32_t dx0[NF];
+    if constexpr (DROP) {
+#pragma unroll
+        for (int f = 0; f < NF; ++f) dx0[f] = dc.k0 + (uint32_t)ql[f] * (uint32_t)(T >> 2) + g;
     }
     TileLd tk, tv;
     tk.load(Kp + (long)kb0 * 64 * ld, ld, tid);
@@ -679,8 +753,15 @@ __global__ void __launch_bounds__(NTA) attn_bwd_dq_kernel(const bf16_t* __restri
                                 if (16 * ki + r < lim) s[f][ki][r] = 0.f;
                         }
                     }
+                    if constexpr (DROP) {
+                        const uint32_t wd = pdrop::word_x(dx0[f] + (uint32_t)((k0 >> 2) + 4 * ki), dc.k1);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) dp[f][ki][r] = s[f][ki][r] * (dp[f][ki][r] - dq_[f]);
+                        for (int r = 0; r < 4; ++r)
+                            dp[f][ki][r] = s[f][ki][r] * ((pdrop::keep(wd, r, dc.thr) ? dp[f][ki][r] * dc.scale : 0.f) - dq_[f]);
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) dp[f][ki][r] = s[f][ki][r] * (dp[f][ki][r] - dq_[f]);
+                    }
                 }
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
@@ -765,10 +846,11 @@ static dim3 attn_grid(int ntile, int H, int B) {
 #endif
 }
 
-template <bool DOC>
+template <bool DOC, bool DROP = false>
 static void launch_fwd(const bf16_t* qkv, bf16_t* out, float* lse2, int B, int T, int H, float scale,
-                       typename MaskSel<DOC>::type mk, hipStream_t st) {
-    hipLaunchKernelGGL(attn_fwd_kernel<DOC>, attn_grid(T / 128, H, B), dim3(NTA), 0, st, qkv, out, lse2, T, H, scale, mk);
+                       typename MaskSel<DOC, DROP>::type mk, hipStream_t st) {
+    hipLaunchKernelGGL((attn_fwd_kernel<DOC, DROP>), attn_grid(T / 128, H, B), dim3(NTA), 0, st, qkv, out, lse2, T, H,
+                       scale, mk);
 }
 
 // qkv [B*T][3*H*64] bf16 -> out [B*T][H*64] bf16, lse2 [B][H][T] fp32.  T % 128 == 0.
@@ -788,42 +870,50 @@ PDNN_API int pdnn_flash_attn_doc_fwd(const bf16_t* qkv, bf16_t* out, float* lse2
     PDNN_LAUNCH_RET;
 }
 
-// DOC at NF = 2 needs no scratch either (profiles/attention_doc_mask.txt), so attn_bwd_wide routes it like the plain one
-template <bool DOC>
+// DOC at NF = 2 needs no scratch either (profiles/attention_doc_mask.txt), so attn_bwd_wide routes it like the plain
+// one.  DROP always takes NF = 1: at NF = 2 the sixteen words per fragment pair bring dK / dV to 254 - 256 VGPRs (no
+// scratch, but one wave / SIMD) and it measured slower than NF = 1 (profiles/attention_dropout.txt), so the NF = 2 DROP
+// kernel is not instantiated
+template <bool DOC, bool DROP = false>
 static void launch_dkdv(const bf16_t* qkv, const bf16_t* dO, const float* lse2, const float* delta, bf16_t* dqkv, int B,
-                        int T, int H, float scale, typename MaskSel<DOC>::type mk, hipStream_t st) {
-    if (pg::tune().attn_bwd_wide & 2)
-        hipLaunchKernelGGL((attn_bwd_dkdv_kernel<2, DOC>), attn_grid(T / 128, H, B), dim3(NTA), 0, st, qkv, dO, lse2,
-                           delta, dqkv, T, H, scale, mk);
-    else
-        hipLaunchKernelGGL((attn_bwd_dkdv_kernel<1, DOC>), attn_grid(T / 64, H, B), dim3(NTA), 0, st, qkv, dO, lse2,
-                           delta, dqkv, T, H, scale, mk);
+                        int T, int H, float scale, typename MaskSel<DOC, DROP>::type mk, hipStream_t st) {
+    if constexpr (!DROP) {
+        if (pg::tune().attn_bwd_wide & 2) {
+            hipLaunchKernelGGL((attn_bwd_dkdv_kernel<2, DOC, false>), attn_grid(T / 128, H, B), dim3(NTA), 0, st, qkv, dO,
+                               lse2, delta, dqkv, T, H, scale, mk);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<1, DOC, DROP>), attn_grid(T / 64, H, B), dim3(NTA), 0, st, qkv, dO, lse2, delta,
+                       dqkv, T, H, scale, mk);
 }
 
-template <bool DELTA, bool DOC>
+template <bool DELTA, bool DOC, bool DROP = false>
 static void launch_dq(const bf16_t* qkv, const bf16_t* out, const bf16_t* dO, const float* lse2, float* delta,
-                      bf16_t* dqkv, int B, int T, int H, float scale, typename MaskSel<DOC>::type mk, hipStream_t st) {
+                      bf16_t* dqkv, int B, int T, int H, float scale, typename MaskSel<DOC, DROP>::type mk,
+                      hipStream_t st) {
     if (pg::tune().attn_bwd_wide & 1)
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<DELTA, 2, DOC>), attn_grid(T / 128, H, B), dim3(NTA), 0, st, qkv, dO, lse2,
-                           delta, out, dqkv, T, H, scale, mk);
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<DELTA, 2, DOC, DROP>), attn_grid(T / 128, H, B), dim3(NTA), 0, st, qkv, dO,
+                           lse2, delta, out, dqkv, T, H, scale, mk);
     else
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<DELTA, 1, DOC>), attn_grid(T / 64, H, B), dim3(NTA), 0, st, qkv, dO, lse2,
-                           delta, out, dqkv, T, H, scale, mk);
+        hipLaunchKernelGGL((attn_bwd_dq_kernel<DELTA, 1, DOC, DROP>), attn_grid(T / 64, H, B), dim3(NTA), 0, st, qkv, dO,
+                           lse2, delta, out, dqkv, T, H, scale, mk);
 }
 
-template <bool DOC>
+template <bool DOC, bool DROP = false>
 static void launch_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dO, const float* lse2, float* delta,
-                       bf16_t* dqkv, int B, int T, int H, float scale, typename MaskSel<DOC>::type mk, hipStream_t st) {
+                       bf16_t* dqkv, int B, int T, int H, float scale, typename MaskSel<DOC, DROP>::type mk,
+                       hipStream_t st) {
     if (pg::tune().attn_delta_in_dq) {       // dQ first (it writes delta), then dK / dV
-        launch_dq<true, DOC>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, mk, st);
-        launch_dkdv<DOC>(qkv, dO, lse2, delta, dqkv, B, T, H, scale, mk, st);
+        launch_dq<true, DOC, DROP>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, mk, st);
+        launch_dkdv<DOC, DROP>(qkv, dO, lse2, delta, dqkv, B, T, H, scale, mk, st);
         return;
     }
     const long n = (long)B * T * H;
     hipLaunchKernelGGL(attn_bwd_delta_kernel, dim3((unsigned)((n + NTA - 1) / NTA)), dim3(NTA), 0, st, out, dO, delta,
                        B * T, T, H);
-    launch_dkdv<DOC>(qkv, dO, lse2, delta, dqkv, B, T, H, scale, mk, st);
-    launch_dq<false, DOC>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, mk, st);
+    launch_dkdv<DOC, DROP>(qkv, dO, lse2, delta, dqkv, B, T, H, scale, mk, st);
+    launch_dq<false, DOC, DROP>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, mk, st);
 }
 
 // dO [B*T][H*64], out/lse2 from the forward -> dqkv [B*T][3*H*64]; delta: fp32 [B][H][T] scratch.
@@ -842,6 +932,46 @@ PDNN_API int pdnn_flash_attn_doc_bwd(const bf16_t* qkv, const bf16_t* out, const
     if (B < 1 || T < 1 || H < 1 || T % 128 || !qkv || !out || !dO || !lse2 || !delta || !dqkv || !doc_start || !doc_end)
         return (int)hipErrorInvalidValue;
     launch_bwd<true>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, DocArg{doc_start, doc_end}, st);
+    PDNN_LAUNCH_RET;
+}
+
+// Causal attention with dropout p on the probabilities (dropout_rng.h): state = device int64[2] (seed, step), read by
+// the kernels; doc_start / doc_end both null (plain causal) or both given (packed documents).  p in [0, 1), quantised
+// to thr / 256; T <= 65536 keeps the granule index inside 32 bits.  The backward takes what the forward took.
+static bool drop_arg(float p, const long long* state, int site, int T, const int* doc_start, const int* doc_end,
+                     pdrop::Arg* a) {
+    uint32_t thr;
+    if (!pdrop::threshold(p, &thr) || !state || site < 0 || T > 65536 || (doc_start == nullptr) != (doc_end == nullptr))
+        return false;
+    *a = pdrop::Arg{state, (uint32_t)site, thr, pdrop::scale_of(thr)};
+    return true;
+}
+
+PDNN_API int pdnn_flash_attn_drop_fwd(const bf16_t* qkv, bf16_t* out, float* lse2, int B, int T, int H, float scale,
+                                      float p, const long long* state, int site, const int* doc_start,
+                                      const int* doc_end, hipStream_t st) {
+    pdrop::Arg a;
+    if (B < 1 || T < 1 || H < 1 || T % 128 || !qkv || !out || !lse2 || !drop_arg(p, state, site, T, doc_start, doc_end, &a))
+        return (int)hipErrorInvalidValue;
+    if (doc_start)
+        launch_fwd<true, true>(qkv, out, lse2, B, T, H, scale, DocDrop{DocArg{doc_start, doc_end}, a}, st);
+    else
+        launch_fwd<false, true>(qkv, out, lse2, B, T, H, scale, CausalDrop{1, a}, st);
+    PDNN_LAUNCH_RET;
+}
+
+PDNN_API int pdnn_flash_attn_drop_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dO, const float* lse2,
+                                      float* delta, bf16_t* dqkv, int B, int T, int H, float scale, float p,
+                                      const long long* state, int site, const int* doc_start, const int* doc_end,
+                                      hipStream_t st) {
+    pdrop::Arg a;
+    if (B < 1 || T < 1 || H < 1 || T % 128 || !qkv || !out || !dO || !lse2 || !delta || !dqkv ||
+        !drop_arg(p, state, site, T, doc_start, doc_end, &a))
+        return (int)hipErrorInvalidValue;
+    if (doc_start)
+        launch_bwd<true, true>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, DocDrop{DocArg{doc_start, doc_end}, a}, st);
+    else
+        launch_bwd<false, true>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, CausalDrop{1, a}, st);
     PDNN_LAUNCH_RET;
 }
 

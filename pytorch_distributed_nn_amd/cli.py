@@ -12,7 +12,9 @@ parameters, biases and normalisation gains, out of the scaling and out of weight
 applies its own fused SGD / Adam, and not with --opt-overlap's per-bucket update),
 --grad-clip NORM (global L2 norm, fused into the optimizer step; 0 = off),
 --label-smoothing EPS and --z-loss Z (training loss only: the fused cross-entropy kernels mix the target with the
-uniform distribution and add Z * logsumexp^2; evaluation reports the plain cross-entropy), --opt-overlap (DDP per-bucket updates),
+uniform distribution and add Z * logsumexp^2; evaluation reports the plain cross-entropy),
+--dropout P (GPT-2: embedding, attention and residual dropout in training forwards, inside the fused kernels;
+--embd-pdrop / --attn-pdrop / --resid-pdrop set one of the three), --opt-overlap (DDP per-bucket updates),
 --n-to-collect (backup workers), --interval-ms, --no-shortcircuit, --evaluator,
 --inject-straggler RANK:MS[,RANK:MS], --straggler-mode (k-of-n inside DDP), --checkpoint-dir, --resume,
 --trace FILE, --metrics FILE.
@@ -65,6 +67,15 @@ def add_fit_args(p: argparse.ArgumentParser):
     p.add_argument("--doc-mask-eot", type=int, default=None, metavar="ID",
                    help="GPT-2: rows are packed documents, each ended by token ID; attention stays inside the "
                         "document (GPT2Config.doc_mask_eot; synthetic token data places ID as its end-of-text)")
+    p.add_argument("--dropout", type=float, default=0.0, metavar="P",
+                   help="GPT-2: dropout on the embedding, the attention probabilities and both residual branches "
+                        "(GPT2Config.embd_pdrop / attn_pdrop / resid_pdrop; training forwards only; quantised to n/256)")
+    p.add_argument("--embd-pdrop", type=float, default=None, metavar="P", help="overrides --dropout for the embedding")
+    p.add_argument("--attn-pdrop", type=float, default=None, metavar="P",
+                   help="overrides --dropout for the attention probabilities (fused attention only: head dim 64, "
+                        "sequence length a multiple of 128)")
+    p.add_argument("--resid-pdrop", type=float, default=None, metavar="P",
+                   help="overrides --dropout for the two residual branches")
     p.add_argument("--opt-overlap", action="store_true",
                    help="DDP: apply each bucket's optimizer update right after its all-reduce, beside the rest of "
                         "the backward (DistributedDataParallel.overlap_optimizer); not with --grad-clip")
@@ -140,12 +151,26 @@ def parse_args(argv=None):
                              f"attention (GPT-2 only)")
         if args.doc_mask_eot < 0:
             raise SystemExit("--doc-mask-eot must be a token id (>= 0)")
+    rates = dropout_rates(args)
+    for flag, v in zip(("--embd-pdrop", "--attn-pdrop", "--resid-pdrop"), rates):
+        if not 0.0 <= v < 1.0:
+            raise SystemExit(f"--dropout / {flag} must be in [0, 1) (0 = off), got {v}")
+    if any(rates):
+        from .models import _ALIASES
+        if not _ALIASES.get(args.network, args.network).lower().startswith("gpt2"):
+            raise SystemExit(f"--dropout and --embd-pdrop / --attn-pdrop / --resid-pdrop belong to GPT-2: network "
+                             f"{args.network} has no such dropout")
     if args.grad_clip and args.opt_overlap:
         raise SystemExit("--grad-clip cannot be combined with --opt-overlap: the overlapped optimizer updates each "
                          "bucket during the backward, before the gradient's global norm exists")
     if args.trust_coef != 1e-3 and args.optimizer != "lars":
         raise SystemExit(f"--trust-coef belongs to --optimizer lars (--optimizer {args.optimizer} has no such factor)")
     return args
+
+
+def dropout_rates(args):
+    """(embd, attn, resid): --dropout, each overridden by its own flag"""
+    return tuple(args.dropout if v is None else v for v in (args.embd_pdrop, args.attn_pdrop, args.resid_pdrop))
 
 
 # flags each mode does not use: given explicitly (or by a YAML config) with a non-default value they are an
@@ -225,6 +250,8 @@ def main(argv=None):
             raise SystemExit(f"--doc-mask-eot {args.doc_mask_eot} is not a token of {args.network} (vocabulary "
                              f"{model.config.vocab_size})")
         model.config.doc_mask_eot = args.doc_mask_eot
+    if any(dropout_rates(args)):
+        model.config.embd_pdrop, model.config.attn_pdrop, model.config.resid_pdrop = dropout_rates(args)
     xdt = torch.bfloat16 if (dev.type == "cuda" and args.dtype in ("bf16", "fp8")) else torch.float32
     # the training loss; evaluation (evaluate below, Trainer.evaluate, evaluator.py) keeps the plain cross-entropy
     train_loss = OF.cross_entropy

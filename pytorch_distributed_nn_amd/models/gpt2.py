@@ -17,6 +17,13 @@ Packed documents (``GPT2Config.doc_mask_eot`` or ``forward(..., doc_bounds=)``):
 documents, each ended by an end-of-text token, attend causally inside their own document only (the DOC kernels of
 ``csrc/kernels/attention.hip``; on the CPU an equivalent boolean mask for SDPA).  The learned absolute positions are
 unchanged: position t of the row, not reset at a document start.
+
+Dropout (``embd_pdrop``, ``attn_pdrop``, ``resid_pdrop``; all 0 by default, GPT-2's own value is 0.1): active in a
+training forward only (``model.training`` and grad mode on).  No mask is stored: every kernel derives its keep bits from
+a (seed, step) pair on the device (``csrc/kernels/dropout_rng.h``), which each training forward snapshots for its own
+backward and then advances, so a captured step draws new masks on every replay.  The pair is a plain attribute created
+on the input's device at the first training forward, seeded from ``torch.initial_seed()`` and the rank; it is no buffer
+and not in ``state_dict``.  The CPU path applies the same bits (``ops.transformer.dropout_keep_reference``).
 """
 from __future__ import annotations
 
@@ -48,6 +55,11 @@ class GPT2Config:
     # packed documents: the id of the end-of-text token that ends (and belongs to) each document of a row; attention
     # then stays inside the document.  None = plain causal attention over the whole row.  Positions are not reset.
     doc_mask_eot: int | None = None
+    # dropout, training forwards only: on wte + wpe, on the attention probabilities (inside the flash kernels: head dim
+    # 64 and T % 128 == 0 only), on each branch's output before its residual add.  Quantised to n / 256.
+    embd_pdrop: float = 0.0
+    attn_pdrop: float = 0.0
+    resid_pdrop: float = 0.0
 
 
 CONFIGS = {
@@ -66,11 +78,16 @@ class Attention(nn.Module):
         self.c_attn = nn.Linear(c.n_embd, 3 * c.n_embd)
         self.c_proj = nn.Linear(c.n_embd, c.n_embd)
 
-    def forward(self, x, mask=None):
+    def forward(self, x, mask=None, keep=None):
         B, T, D = x.shape
         q, k, v = self.c_attn(x).split(D, dim=2)
         q, k, v = (t.view(B, T, self.n_head, D // self.n_head).transpose(1, 2) for t in (q, k, v))
-        if mask is not None:        # bool [B][1][T][T], True = visible (causal and inside the document)
+        if keep is not None:        # [B][H][T][T]: keep / (1 - p) on the probabilities, after the softmax
+            i = torch.arange(T, device=x.device)
+            vis = mask if mask is not None else (i[None, :] <= i[:, None])
+            att = (q @ k.transpose(-1, -2)) / math.sqrt(D // self.n_head)
+            y = (torch.softmax(att.masked_fill(~vis, float("-inf")), -1) * keep) @ v
+        elif mask is not None:      # bool [B][1][T][T], True = visible (causal and inside the document)
             y = F.scaled_dot_product_attention(q, k, v, attn_mask=mask)
         else:
             y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
@@ -95,9 +112,15 @@ class Block(nn.Module):
         self.ln_2 = nn.LayerNorm(c.n_embd, eps=c.eps)
         self.mlp = MLP(c)
 
-    def forward(self, x, mask=None):
-        x = x + self.attn(self.ln_1(x), mask)
-        return x + self.mlp(self.ln_2(x))
+    def forward(self, x, mask=None, drop=None):
+        if drop is None:
+            x = x + self.attn(self.ln_1(x), mask)
+            return x + self.mlp(self.ln_2(x))
+        keep, r1, r2 = drop         # scaled keep factors (or None): probabilities, attention branch, MLP branch
+        a = self.attn(self.ln_1(x), mask, keep)
+        x = x + (a * r1 if r1 is not None else a)
+        m = self.mlp(self.ln_2(x))
+        return x + (m * r2 if r2 is not None else m)
 
     def fp8_metas(self, device):
         metas = getattr(self, "_fp8_metas", None)
@@ -192,6 +215,32 @@ class GPT2(nn.Module):
             return K.doc_bounds(idx.long().contiguous(), int(eot))
         return TX.doc_bounds_reference(idx, int(eot))
 
+    def dropout_rates(self):
+        """(embd, attn, resid) of this forward: the config's in a training forward, else None"""
+        c = self.config
+        rates = (c.embd_pdrop, c.attn_pdrop, c.resid_pdrop)
+        for name, p in zip(("embd_pdrop", "attn_pdrop", "resid_pdrop"), rates):
+            if not 0.0 <= p < 1.0:
+                raise ValueError(f"GPT2Config.{name} must be in [0, 1), got {p!r}")
+        return rates if self.training and torch.is_grad_enabled() and any(rates) else None
+
+    def dropout_state(self, device):
+        """The int64 (seed, step) pair the dropout kernels read, on ``device`` (created, or moved, on demand)."""
+        st = self.__dict__.get("_pdnn_drop_state")
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if st is None or st.device != device:
+            pair = st.tolist() if st is not None else [TX.dropout_seed(), 0]
+            st = self.__dict__["_pdnn_drop_state"] = torch.tensor(pair, dtype=torch.int64, device=device)
+        return st
+
+    def set_dropout_state(self, seed, step=0, device=None):
+        """Restart the mask sequence: the next training forward draws the masks of (seed, step)."""
+        device = device if device is not None else next(self.parameters()).device
+        self.__dict__["_pdnn_drop_state"] = torch.tensor([int(seed) & ((1 << 63) - 1), int(step)], dtype=torch.int64,
+                                                         device=device)
+
     def forward(self, idx, targets=None, doc_bounds=None):
         """``doc_bounds``: optional (doc_start, doc_end), integer [B][T], for callers that pack themselves (first token
         of t's document, one past its last); otherwise config.doc_mask_eot, when set, derives them from ``idx`` once
@@ -200,8 +249,11 @@ class GPT2(nn.Module):
         c = self.config
         assert T <= c.block_size, f"sequence length {T} > block size {c.block_size}"
         doc = self._doc_bounds(idx, doc_bounds)
+        rates = self.dropout_rates()
+        # one snapshot of (seed, step) per training forward, for every Function of it; the live state moves on
+        snap = TX.dropout_advance(self.dropout_state(idx.device)) if rates is not None else None
         if not idx.is_cuda:
-            return self._forward_reference(idx, targets, doc)
+            return self._forward_reference(idx, targets, doc, (rates, snap) if rates is not None else None)
         tr = self.transformer
         wte, wpe = tr.wte.weight, tr.wpe.weight
         pf = tuning.get("wt_prefetch")
@@ -214,16 +266,21 @@ class GPT2(nn.Module):
         # tied wte: with targets the fused LM head and the embedding both accumulate into its arena gradient
         hd = targets is not None and direct_grad(wte) is not None
         ddp = self._row_tail() if hd and torch.is_grad_enabled() else None
+        edrop = (rates[0], snap) if rates is not None and rates[0] else None
         if ddp is not None:
             # split under DistributedDataParallel: the head announces wte, the embedding's rows go through
             # ddp.reduce_sparse_rows (wte is not an autograd input of the embedding)
-            x = TX.EmbeddingFn.apply(idx.reshape(-1).long().contiguous(), T, wte_k, wpe_k, None, wpe, False, (ddp, wte))
+            x = TX.EmbeddingFn.apply(idx.reshape(-1).long().contiguous(), T, wte_k, wpe_k, None, wpe, False, (ddp, wte),
+                                     edrop)
         else:
-            x = TX.EmbeddingFn.apply(idx.reshape(-1).long().contiguous(), T, wte_k, wpe_k, wte, wpe, hd)
-        for blk in tr.h:
+            x = TX.EmbeddingFn.apply(idx.reshape(-1).long().contiguous(), T, wte_k, wpe_k, wte, wpe, hd, None, edrop)
+        for layer, blk in enumerate(tr.h):
             params, shadows = blk.fused_params()
             metas = blk.fp8_metas(x.device) if c.fp8 else None
-            x = TX.GPT2BlockFn.apply(x, (B, T, c.n_head, c.eps, metas, doc), shadows, *params)
+            conf = (B, T, c.n_head, c.eps, metas, doc)
+            if rates is not None and (rates[1] or rates[2]):
+                conf += ((rates[1], rates[2], snap, layer),)
+            x = TX.GPT2BlockFn.apply(x, conf, shadows, *params)
         if targets is None:
             xf = TX.layer_norm(x, tr.ln_f.weight, tr.ln_f.bias, c.eps)
             return OF.linear(xf, wte).view(B, T, -1)
@@ -232,9 +289,16 @@ class GPT2(nn.Module):
                                      tr.ln_f.bias, wte, hd, ddp is not None, train,
                                      c.label_smoothing if train else 0.0, c.z_loss if train else 0.0)
 
-    def _forward_reference(self, idx, targets=None, doc=None):
+    def _forward_reference(self, idx, targets=None, doc=None, drop=None):
         B, T = idx.shape
         mask = TX.doc_visible(doc[0]).unsqueeze(1) if doc is not None else None
+        c = self.config
+
+        def keep(p, site, **shape):     # the kernels' bits for this site, times 1 / (1 - p_eff); None for p = 0
+            if not p:
+                return None
+            bits = TX.dropout_keep_reference(drop[1], site, p, device=idx.device, **shape)
+            return bits.to(tr.wte.weight.dtype) * TX.dropout_scale(p)
         tr = self.transformer
         pos = torch.arange(T, device=idx.device)
         ddp = self._row_tail() if targets is not None and torch.is_grad_enabled() else None
@@ -242,13 +306,23 @@ class GPT2(nn.Module):
             x = _RowTailEmbedding.apply(idx, tr.wte.weight.detach(), tr.wpe(pos), (ddp, tr.wte.weight))
         else:
             x = tr.wte(idx) + tr.wpe(pos)
-        for blk in tr.h:
-            x = blk(x, mask)
+        if drop is None:
+            for blk in tr.h:
+                x = blk(x, mask)
+        else:
+            pe, pa, pr = drop[0]
+            ke = keep(pe, TX.SITE_EMBD, rows=(B * T, c.n_embd))
+            if ke is not None:
+                x = x * ke.view(B, T, -1)
+            for layer, blk in enumerate(tr.h):
+                r1, r2 = (keep(pr, 4 * layer + s, rows=(B * T, c.n_embd)) for s in (1, 2))
+                x = blk(x, mask, (keep(pa, 4 * layer, attn=(B, c.n_head, T)),
+                                  r1.view(B, T, -1) if r1 is not None else None,
+                                  r2.view(B, T, -1) if r2 is not None else None))
         logits = self.lm_head(tr.ln_f(x))
         if targets is None:
             return logits
         lg, t = logits.float().view(-1, logits.shape[-1]), targets.reshape(-1)
-        c = self.config
         if not torch.is_grad_enabled() or not (c.label_smoothing or c.z_loss):
             return F.cross_entropy(lg, t)
         loss = F.cross_entropy(lg, t, label_smoothing=c.label_smoothing)

@@ -144,6 +144,12 @@ _SIGS = {
     "pdnn_flash_attn_doc_fwd": [P, P, P, I, I, I, F, P, P, P],
     "pdnn_flash_attn_doc_bwd": [P, P, P, P, P, P, I, I, I, F, P, P, P],
     "pdnn_doc_bounds": [P, ctypes.c_longlong, P, P, I, I, P],
+    "pdnn_flash_attn_drop_fwd": [P, P, P, I, I, I, F, F, P, I, P, P, P],
+    "pdnn_flash_attn_drop_bwd": [P, P, P, P, P, P, I, I, I, F, F, P, I, P, P, P],
+    "pdnn_dropout_add_fwd": [P, P, P, L, I, F, P, I, P],
+    "pdnn_dropout_bwd": [P, P, L, I, F, P, I, P],
+    "pdnn_dropout_mask_rows": [P, L, I, F, P, I, P],
+    "pdnn_dropout_mask_attn": [P, I, I, I, F, P, I, P],
     "pdnn_embedding_fwd": [P, P, P, P, I, I, I, P],
     "pdnn_embedding_bwd": [P, P, P, P, I, I, I, P],
     "pdnn_embedding_bwd_scaled": [P, P, P, P, I, I, I, F, P],
@@ -195,6 +201,9 @@ def _load():
             continue
         fn.argtypes = argtypes
         fn.restype = ctypes.c_int
+    if getattr(lib, "pdnn_dropout_p_eff", None) is not None:     # float -> float, not a launcher
+        lib.pdnn_dropout_p_eff.argtypes = [F]
+        lib.pdnn_dropout_p_eff.restype = F
     if getattr(lib, "pdnn_tune_error", None) is not None:
         lib.pdnn_tune_error.restype = ctypes.c_char_p
         lib.pdnn_tune_unknown.restype = ctypes.c_char_p

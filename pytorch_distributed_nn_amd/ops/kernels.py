@@ -1486,6 +1486,119 @@ def flash_attn_doc_bwd(qkv, out, dout, lse2, doc_start, doc_end, B, T, H, scale)
     return dqkv
 
 
+# ----------------------------------------------------------------------------------- dropout (csrc/kernels/dropout_rng.h)
+def dropout_p_eff(p):
+    """The probability the kernels use for ``p``: quantised to thr / 256 (the scale is 1 / (1 - p_eff))."""
+    pe = float(lib().pdnn_dropout_p_eff(float(p)))
+    _chk(pe >= 0.0, f"dropout: p must be in [0, 1), got {p!r}")
+    return pe
+
+
+def _drop_chk(name, p, state, site, dev):
+    p = float(p)
+    _chk(0.0 <= p < 1.0, f"{name}: p must be in [0, 1), got {p!r}")
+    _chk(torch.is_tensor(state) and state.dtype == torch.int64 and state.shape == (2,) and state.is_contiguous()
+         and state.device == dev, f"{name}: the dropout state must be a contiguous int64 [2] (seed, step) on {dev}")
+    _chk(isinstance(site, int) and not isinstance(site, bool) and 0 <= site < 2 ** 31, f"{name}: site {site!r}")
+    return p
+
+
+def _rows_chk(name, x, p, state, site):
+    _bf16_c(x, name)
+    _chk(x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 8 and x.shape[1] % 8 == 0
+         and x.shape[0] * (x.shape[1] // 4) <= 2 ** 32, f"{name}: expected bf16 [R][D], D % 8 == 0, got {tuple(x.shape)}")
+    return _drop_chk(name, p, state, site, x.device)
+
+
+def dropout_add_fwd(x, res, p, state, site, out=None):
+    """y = res + keep o x / (1 - p_eff) on bf16 [R][D]; ``res`` may be None, ``out`` may be ``x`` itself.  The keep bits
+    are the generator's for (state = int64 [seed, step] on the device, site, (row, col))."""
+    p = _rows_chk("dropout_add_fwd.x", x, p, state, site)
+    if res is not None:
+        _bf16_c(res, "dropout_add_fwd.res")
+        _chk(res.shape == x.shape, "dropout_add_fwd: res must have x's shape")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _bf16_c(out, "dropout_add_fwd.out")
+        _chk(out.shape == x.shape and out.device == x.device, "dropout_add_fwd: out must have x's shape")
+    call("pdnn_dropout_add_fwd", ptr(x), ptr(res), ptr(out), x.shape[0], x.shape[1], p, ptr(state), site, stream())
+    return out
+
+
+def dropout_bwd(g, p, state, site):
+    """dx = keep o g / (1 - p_eff): the bits dropout_add_fwd used for the same (state, site)."""
+    g = g.contiguous()
+    p = _rows_chk("dropout_bwd.g", g, p, state, site)
+    dx = torch.empty_like(g)
+    call("pdnn_dropout_bwd", ptr(g), ptr(dx), g.shape[0], g.shape[1], p, ptr(state), site, stream())
+    return dx
+
+
+def dropout_mask_rows(R, D, p, state, site):
+    """uint8 [R][D], 1 = kept: the generator's bits for a row op (tests, CPU parity)."""
+    _chk(R >= 1 and D >= 8 and D % 8 == 0 and R * (D // 4) <= 2 ** 32, f"dropout_mask_rows: R={R} D={D}")
+    p = _drop_chk("dropout_mask_rows", p, state, site, state.device if torch.is_tensor(state) else None)
+    _chk(state.is_cuda, "dropout_mask_rows: CUDA state")
+    out = torch.empty(R, D, device=state.device, dtype=torch.uint8)
+    call("pdnn_dropout_mask_rows", ptr(out), R, D, p, ptr(state), site, stream())
+    return out
+
+
+def dropout_mask_attn(B, H, T, p, state, site):
+    """uint8 [B][H][T(q)][T(k)], 1 = kept: the generator's bits for the attention probabilities."""
+    _chk(B >= 1 and H >= 1 and T >= 4 and T % 4 == 0 and T <= 65536, f"dropout_mask_attn: B={B} H={H} T={T}")
+    p = _drop_chk("dropout_mask_attn", p, state, site, state.device if torch.is_tensor(state) else None)
+    _chk(state.is_cuda, "dropout_mask_attn: CUDA state")
+    out = torch.empty(B, H, T, T, device=state.device, dtype=torch.uint8)
+    call("pdnn_dropout_mask_attn", ptr(out), B, H, T, p, ptr(state), site, stream())
+    return out
+
+
+def flash_attn_drop_fwd(qkv, B, T, H, scale, p, state, site, doc_start=None, doc_end=None):
+    """flash_attn_fwd (or flash_attn_doc_fwd, with bounds) with dropout ``p`` on the probabilities: O = (P o keep) V /
+    (1 - p_eff); lse2 is that of the undropped softmax.  p == 0 runs the plain / DOC entry."""
+    _bf16_c(qkv, "flash_attn_drop.qkv")
+    _chk(B >= 1 and T >= 1 and H >= 1 and qkv.shape == (B * T, 3 * H * 64) and T % 128 == 0 and T <= 65536,
+         f"flash_attn_drop: qkv {tuple(qkv.shape)} B={B} T={T} H={H}")
+    p = _drop_chk("flash_attn_drop", p, state, site, qkv.device)
+    _chk((doc_start is None) == (doc_end is None), "flash_attn_drop: doc_start and doc_end go together")
+    if doc_start is not None:
+        _doc_chk("flash_attn_drop", doc_start, doc_end, B, T, qkv.device)
+    if p == 0.0:
+        return (flash_attn_fwd(qkv, B, T, H, scale) if doc_start is None
+                else flash_attn_doc_fwd(qkv, doc_start, doc_end, B, T, H, scale))
+    out = torch.empty(B * T, H * 64, device=qkv.device, dtype=BF16)
+    lse2 = torch.empty(B, H, T, device=qkv.device, dtype=F32)
+    call("pdnn_flash_attn_drop_fwd", ptr(qkv), ptr(out), ptr(lse2), B, T, H, float(scale), p, ptr(state), site,
+         ptr(doc_start), ptr(doc_end), stream())
+    return out, lse2
+
+
+def flash_attn_drop_bwd(qkv, out, dout, lse2, B, T, H, scale, p, state, site, doc_start=None, doc_end=None):
+    _bf16_c(qkv, "flash_attn_drop_bwd.qkv")
+    _chk(B >= 1 and T >= 1 and H >= 1 and qkv.shape == (B * T, 3 * H * 64) and T % 128 == 0 and T <= 65536,
+         f"flash_attn_drop_bwd: qkv {tuple(qkv.shape)} B={B} T={T} H={H}")
+    p = _drop_chk("flash_attn_drop_bwd", p, state, site, qkv.device)
+    _chk((doc_start is None) == (doc_end is None), "flash_attn_drop_bwd: doc_start and doc_end go together")
+    if doc_start is not None:
+        _doc_chk("flash_attn_drop_bwd", doc_start, doc_end, B, T, qkv.device)
+    if p == 0.0:
+        return (flash_attn_bwd(qkv, out, dout, lse2, B, T, H, scale) if doc_start is None
+                else flash_attn_doc_bwd(qkv, out, dout, lse2, doc_start, doc_end, B, T, H, scale))
+    dout = dout.contiguous()
+    _chk(out.dtype == BF16 and out.shape == (B * T, H * 64) and out.is_contiguous(),
+         "flash_attn_drop_bwd: out must be contiguous bf16 [B*T][H*64]")
+    _chk(dout.dtype == BF16 and dout.shape == out.shape, "flash_attn_drop_bwd: dout must be bf16 of out's shape")
+    _chk(lse2.dtype == F32 and lse2.shape == (B, H, T) and lse2.is_contiguous(),
+         "flash_attn_drop_bwd: lse2 must be contiguous fp32 [B][H][T]")
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty(B, H, T, device=qkv.device, dtype=F32)
+    call("pdnn_flash_attn_drop_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse2), ptr(delta), ptr(dqkv), B, T, H,
+         float(scale), p, ptr(state), site, ptr(doc_start), ptr(doc_end), stream())
+    return dqkv
+
+
 def embedding_fwd(idx, wte, wpe, T):
     R = idx.numel()
     D = wte.shape[1]

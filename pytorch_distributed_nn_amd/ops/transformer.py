@@ -132,6 +132,93 @@ def doc_visible(doc_start):
 
 
 # ------------------------------------------------------------------------------------------------
+# dropout: the counter-based generator of csrc/kernels/dropout_rng.h in torch integers (any device), and the
+# (seed, step) state of a model
+# ------------------------------------------------------------------------------------------------
+SITE_EMBD = 0x7fffffff      # site = 4 * layer + {0 attention probabilities, 1 attention residual, 2 MLP residual}
+_M32, _M64 = (1 << 32) - 1, (1 << 64) - 1
+
+
+def dropout_threshold(p):
+    """p in [0, 1) -> thr in [0, 255]: an element is kept iff its byte >= thr, p_eff = thr / 256"""
+    p32 = torch.tensor(float(p), dtype=F32).item()
+    if not 0.0 <= p32 < 1.0:
+        raise ValueError(f"dropout: p must be in [0, 1), got {p!r}")
+    return min(255, int(p32 * 256.0 + 0.5))
+
+
+def dropout_p_eff(p):
+    return dropout_threshold(p) / 256.0
+
+
+def dropout_scale(p):
+    return 256.0 / (256 - dropout_threshold(p))
+
+
+def _mix64(z):
+    z ^= z >> 30
+    z = (z * 0xBF58476D1CE4E5B9) & _M64
+    z ^= z >> 27
+    z = (z * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def _drop_key(seed, step, site, stream):
+    z = _mix64(((seed & _M64) + 0x9E3779B97F4A7C15 * ((step & _M64) + 1)) & _M64)
+    z = _mix64(z ^ ((site << 32) | stream))
+    return z & _M32, z >> 32
+
+
+def _mul32(x, c):
+    """x * c mod 2^32 on an int64 tensor holding 32-bit values, without leaving 63 bits"""
+    return (x * (c & 0xFFFF) + (((x * (c >> 16)) & 0xFFFF) << 16)) & _M32
+
+
+def _drop_words(k0, k1, idx):
+    x = (idx + k0) & _M32
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x7feb352d)
+    x = x ^ (x >> 15)
+    x = (x + k1) & _M32
+    x = _mul32(x, 0x846ca68b)
+    return x ^ (x >> 16)
+
+
+def dropout_keep_reference(state, site, p, rows=None, attn=None, device="cpu"):
+    """The keep bits of the dropout kernels (bool): ``rows`` = (R, D) -> [R][D] for a row op, ``attn`` = (B, H, T) ->
+    [B][H][T(q)][T(k)] for the attention probabilities.  ``state`` = the int64 (seed, step) tensor, or the pair."""
+    seed, step = (int(v) for v in (state.tolist() if torch.is_tensor(state) else state))
+    thr = dropout_threshold(p)
+    sh = 8 * torch.arange(4, device=device)
+
+    def bits(k, n, shape):
+        w = _drop_words(k[0], k[1], torch.arange(n, device=device, dtype=torch.int64))
+        return (((w[:, None] >> sh) & 255) >= thr).reshape(shape)
+
+    if rows is not None:
+        R, D = rows
+        return bits(_drop_key(seed, step, site, 0), R * (D // 4), (R, D))
+    B, H, T = attn
+    return torch.stack([bits(_drop_key(seed, step, site, s), T * (T // 4), (T, T)) for s in range(B * H)]).view(B, H, T, T)
+
+
+def dropout_seed():
+    """torch's initial seed folded with the rank, so ranks draw different masks; kept inside int64"""
+    import torch.distributed as dist
+    rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+    return (torch.initial_seed() + 0x9E3779B97F4A7C15 * rank) & ((1 << 63) - 1)
+
+
+def dropout_advance(state):
+    """One training forward: -> a fresh snapshot of (seed, step) for this forward's Functions (and their backward, so
+    that a forward run in between does not change its masks); ``state`` then counts one step further.  Two
+    stream-ordered device ops, captured with the step: a replay reads and advances the live state."""
+    snap = state.clone()
+    state[1:].add_(1)
+    return snap
+
+
+# ------------------------------------------------------------------------------------------------
 # LayerNorm
 # ------------------------------------------------------------------------------------------------
 class _LayerNorm(torch.autograd.Function):
@@ -161,18 +248,24 @@ def layer_norm(x, weight, bias, eps=1e-5):
 # ------------------------------------------------------------------------------------------------
 class EmbeddingFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, idx, T, wte_k, wpe_k, wte, wpe, head_direct=False, tail=None):
+    def forward(ctx, idx, T, wte_k, wpe_k, wte, wpe, head_direct=False, tail=None, drop=None):
         ctx.save_for_backward(idx)
         ctx.conf = (T, wte_k.shape, wpe.shape)
         ctx.wpe, ctx.wte = wpe, wte
         ctx.head_direct = head_direct       # the tied LM head accumulates its wte gradient in the arena too
         ctx.tail = tail                     # (ddp, wte): split tied embedding, wte is NOT an input (wte=None)
-        return K.embedding_fwd(idx, wte_k, wpe_k, T)
+        ctx.drop = drop                     # (p, state snapshot): dropout on wte + wpe
+        x = K.embedding_fwd(idx, wte_k, wpe_k, T)
+        if drop is not None:
+            K.dropout_add_fwd(x, None, drop[0], drop[1], SITE_EMBD, out=x)
+        return x
 
     @staticmethod
     def backward(ctx, g):
         (idx,) = ctx.saved_tensors
         T, s_te, s_pe = ctx.conf
+        if ctx.drop is not None:            # the rows both tables receive are the masked ones
+            g = K.dropout_bwd(g, ctx.drop[0], ctx.drop[1], SITE_EMBD)
         if ctx.tail is not None:
             # split tied embedding (parallel/ddp.py reduce_sparse_rows): the LM head's dense gradient was announced
             # (and its bucket all-reduced) at the start of the backward; these B*T rows are gathered from every rank
@@ -188,7 +281,7 @@ class EmbeddingFn(torch.autograd.Function):
             gw = wte.grad
             ddp.reduce_sparse_rows(wte, idx, g, lambda i, r, sc: K.embedding_bwd(i, r, gw, None, T, scale=sc))
             ctx.wpe = ctx.wte = None
-            return None, None, None, None, None, dwpe, None, None
+            return None, None, None, None, None, dwpe, None, None, None
         # wte is tied with the LM head, whose backward ran first and (with a flat arena) already accumulated
         # its part in place: the embedding adds its rows on top (atomics) and announces the parameter, so no
         # zero-filled temporaries and no autograd sum of the two gradients
@@ -204,7 +297,7 @@ class EmbeddingFn(torch.autograd.Function):
             grad_ready(ctx.wte)
             dwte = None
         ctx.wpe = ctx.wte = None
-        return None, None, None, None, dwte, dwpe, None, None
+        return None, None, None, None, dwte, dwpe, None, None, None
 
 
 # ------------------------------------------------------------------------------------------------
@@ -304,6 +397,8 @@ class GPT2BlockFn(torch.autograd.Function):
         B, T, H, eps = conf[:4]
         metas = conf[4] if len(conf) > 4 else None
         doc = conf[5] if len(conf) > 5 else None        # (doc_start, doc_end) int32 [B][T]: packed-document mask
+        # (attn_pdrop, resid_pdrop, state snapshot, layer) of a training forward with dropout, else None
+        p_attn, p_res, dstate, layer = (conf[6] if len(conf) > 6 and conf[6] is not None else (0.0, 0.0, None, 0))
         ln1w, ln1b, _, attn_b, _, proj_b, ln2w, ln2b, _, fc_b, _, fc2_b = params
         wqkv, wproj, wfc, wfc2 = shadows
         if metas is not None:
@@ -321,7 +416,14 @@ class GPT2BlockFn(torch.autograd.Function):
         if doc is not None and not flash:
             raise ValueError(f"packed-document attention needs the fused kernels (head dim 64, T % 128 == 0); got head "
                              f"dim {D // H}, T = {T}: the unfused attention chain has no document mask")
-        if doc is not None:
+        if p_attn > 0 and not flash:
+            raise ValueError(f"attention dropout needs the fused kernels (head dim 64, T % 128 == 0); got head dim "
+                             f"{D // H}, T = {T}: the unfused attention chain has no dropout (attn_pdrop = 0 runs it)")
+        if p_attn > 0:      # the probabilities never leave the kernel's registers: the mask is drawn inside it
+            y, P = K.flash_attn_drop_fwd(qkv, B, T, H, 1.0 / math.sqrt(D // H), p_attn, dstate, 4 * layer,
+                                         *(doc if doc is not None else (None, None)))
+            S = None
+        elif doc is not None:
             y, P = K.flash_attn_doc_fwd(qkv, doc[0], doc[1], B, T, H, 1.0 / math.sqrt(D // H))
             S = None
         elif flash:
@@ -329,11 +431,19 @@ class GPT2BlockFn(torch.autograd.Function):
             S = None
         else:
             y, P, S = attention_fwd(qkv, B, T, H)
-        x1 = lin(y, 4, wproj, bias=proj_b, res=x)
+        if p_res > 0:       # the branch output is dropped before the add: GEMM with bias only, then one row pass
+            x1 = lin(y, 4, wproj, bias=proj_b)
+            K.dropout_add_fwd(x1, x, p_res, dstate, 4 * layer + 1, out=x1)
+        else:
+            x1 = lin(y, 4, wproj, bias=proj_b, res=x)
         ln2, m2, r2 = K.layernorm_fwd(x1, ln2w, ln2b, eps)
         u = torch.empty(x.shape[0], wfc.shape[0], device=x.device, dtype=BF16)
         h = lin(ln2, 8, wfc, bias=fc_b, act=2, aux=u)
-        x2 = lin(h, 10, wfc2, bias=fc2_b, res=x1)
+        if p_res > 0:
+            x2 = lin(h, 10, wfc2, bias=fc2_b)
+            K.dropout_add_fwd(x2, x1, p_res, dstate, 4 * layer + 2, out=x2)
+        else:
+            x2 = lin(h, 10, wfc2, bias=fc2_b, res=x1)
         ctx.save_for_backward(x, ln1, m1, r1, qkv, P, y, x1, ln2, m2, r2, u, h, ln1w, ln2w, *shadows)
         ctx.conf = conf
         ctx.flash = flash
@@ -353,17 +463,24 @@ class GPT2BlockFn(torch.autograd.Function):
             # the four data-gradient GEMMs' transposed weights of this block in one launch, just before use
             from .functional import prefetch_weight_t
             prefetch_weight_t((Pm[10], Pm[8], Pm[4], Pm[2]))
-        # MLP
-        du = BL.linear_dgrad(g, wfc2, dgelu=u, p=Pm[10])                       # (g . Wfc2) * gelu'(u)
-        dfc2_w, dfc2_b = sink.linear(Pm[10], Pm[11], g, h)
+        p_attn, p_res, dstate, layer = (ctx.conf[6] if len(ctx.conf) > 6 and ctx.conf[6] is not None
+                                        else (0.0, 0.0, None, 0))
+        # MLP (resid_pdrop: the branch sees the masked gradient, the residual path -- LN2's dres -- the whole one)
+        gm = K.dropout_bwd(g, p_res, dstate, 4 * layer + 2) if p_res > 0 else g
+        du = BL.linear_dgrad(gm, wfc2, dgelu=u, p=Pm[10])                      # (g . Wfc2) * gelu'(u)
+        dfc2_w, dfc2_b = sink.linear(Pm[10], Pm[11], gm, h)
         dln2 = BL.linear_dgrad(du, wfc, p=Pm[8])
         dfc_w, dfc_b = sink.linear(Pm[8], Pm[9], du, ln2)
         dx1, dln2w, dln2b = sink.layernorm(dln2, x1, ln2w, m2, r2, g, Pm[6], Pm[7])
         # attention
-        dy = BL.linear_dgrad(dx1, wproj, p=Pm[4])
-        dproj_w, dproj_b = sink.linear(Pm[4], Pm[5], dx1, y)
+        dm = K.dropout_bwd(dx1, p_res, dstate, 4 * layer + 1) if p_res > 0 else dx1
+        dy = BL.linear_dgrad(dm, wproj, p=Pm[4])
+        dproj_w, dproj_b = sink.linear(Pm[4], Pm[5], dm, y)
         doc = ctx.conf[5] if len(ctx.conf) > 5 else None
-        if doc is not None:
+        if p_attn > 0:
+            dqkv = K.flash_attn_drop_bwd(qkv, y, dy, P, B, T, H, 1.0 / math.sqrt(x.shape[1] // H), p_attn, dstate,
+                                         4 * layer, *(doc if doc is not None else (None, None)))
+        elif doc is not None:
             dqkv = K.flash_attn_doc_bwd(qkv, y, dy, P, doc[0], doc[1], B, T, H, 1.0 / math.sqrt(x.shape[1] // H))
         elif ctx.flash:
             dqkv = K.flash_attn_bwd(qkv, y, dy, P, B, T, H, 1.0 / math.sqrt(x.shape[1] // H))

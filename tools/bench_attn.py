@@ -5,6 +5,9 @@
         packed documents of N tokens at B8 / T1024 / H12: the DOC kernels and the plain causal ones alternate in one
         process, ROUNDS times; medians, the plain kernel's own spread across the rounds, and the ratio beside the work
         ratio sum(len^2) / T^2
+    python tools/bench_attn.py --dropout 0.1 [--seq-len 4096] [--doc-len 256] [--bwd-wide 1] [--rounds 7]
+        dropout P on the probabilities (the DROP kernels) against the kernels without it, at B8 / T / H12, the pairs
+        alternating in one process; with --doc-len both sides run under the packed-document mask
 """
 import argparse
 import json
@@ -63,11 +66,54 @@ def doc_main(doc_len, rounds):
     print(json.dumps(rnd(r)), flush=True)
 
 
+def drop_main(p, T, doc_len, rounds, bwd_wide):
+    B, H = 8, 12
+    sc = 1 / math.sqrt(64)
+    if bwd_wide is not None:
+        K.tune_set("attn_bwd_wide", bwd_wide)
+    qkv = (torch.randn(B * T, 3 * H * 64, device="cuda") * 0.5).to(torch.bfloat16)
+    ds = de = None
+    if doc_len:
+        t = torch.arange(T, device="cuda", dtype=torch.int32)
+        ds = (t // doc_len * doc_len).expand(B, T).contiguous()
+        de = (ds + doc_len).clamp_max(T).contiguous()
+    st = torch.tensor([1, 0], dtype=torch.int64, device="cuda")
+    out, lse = K.flash_attn_drop_fwd(qkv, B, T, H, sc, 0.0, st, 0, ds, de)          # p = 0: the plain / DOC entry
+    outd, lsed = K.flash_attn_drop_fwd(qkv, B, T, H, sc, p, st, 0, ds, de)
+    do = torch.randn_like(out)
+    fns = {"base_fwd": lambda: K.flash_attn_drop_fwd(qkv, B, T, H, sc, 0.0, st, 0, ds, de),
+           "drop_fwd": lambda: K.flash_attn_drop_fwd(qkv, B, T, H, sc, p, st, 0, ds, de),
+           "base_bwd": lambda: K.flash_attn_drop_bwd(qkv, out, do, lse, B, T, H, sc, 0.0, st, 0, ds, de),
+           "drop_bwd": lambda: K.flash_attn_drop_bwd(qkv, outd, do, lsed, B, T, H, sc, p, st, 0, ds, de)}
+    times = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            times[k].append(timeit(fn, iters=50 if T <= 1024 else 10))
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    r = {"B": B, "T": T, "H": H, "p": p, "p_eff": K.dropout_p_eff(p), "doc_len": doc_len, "rounds": rounds,
+         "attn_bwd_wide": K.tune_get("attn_bwd_wide")}
+    for d in ("fwd", "bwd"):
+        a, b = times["base_" + d], times["drop_" + d]
+        r[d] = {"base_us": med["base_" + d], "drop_us": med["drop_" + d], "ratio": med["drop_" + d] / med["base_" + d],
+                "base_min_max_us": [min(a), max(a)], "drop_min_max_us": [min(b), max(b)],
+                "base_spread": (max(a) - min(a)) / med["base_" + d]}
+    rnd = lambda v: round(v, 3) if isinstance(v, float) else ([rnd(x) for x in v] if isinstance(v, list) else  # noqa: E731
+                                                              ({k: rnd(x) for k, x in v.items()} if isinstance(v, dict) else v))
+    print(json.dumps(rnd(r)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dropout", type=float, default=0.0, metavar="P", help="the DROP kernels at P vs the ones without")
+    ap.add_argument("--seq-len", type=int, default=1024, help="--dropout: T (a multiple of 128)")
+    ap.add_argument("--bwd-wide", type=int, default=None, help="--dropout: attn_bwd_wide of both sides (default: tuning)")
     ap.add_argument("--doc-len", type=int, default=0, help="packed documents of N tokens vs the plain causal kernels")
     ap.add_argument("--rounds", type=int, default=7)
     a = ap.parse_args()
+    if a.dropout:
+        if not 0.0 < a.dropout < 1.0 or a.seq_len % 128 or a.doc_len < 0:
+            raise SystemExit("--dropout must be in (0, 1), --seq-len a multiple of 128")
+        return drop_main(a.dropout, a.seq_len, a.doc_len, a.rounds, a.bwd_wide)
     if a.doc_len:
         if a.doc_len < 1:
             raise SystemExit("--doc-len must be >= 1")
