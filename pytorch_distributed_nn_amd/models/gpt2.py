@@ -24,6 +24,10 @@ a (seed, step) pair on the device (``csrc/kernels/dropout_rng.h``), which each t
 backward and then advances, so a captured step draws new masks on every replay.  The pair is a plain attribute created
 on the input's device at the first training forward, seeded from ``torch.initial_seed()`` and the rank; it is no buffer
 and not in ``state_dict``.  The CPU path applies the same bits (``ops.transformer.dropout_keep_reference``).
+
+Generation (``generate``): one prefill over the prompt, then one single-token step per new token against a key/value
+cache (GPU: ``ops.transformer.KVCache`` / ``block_prefill`` / ``block_decode`` on ``csrc/kernels/attention_decode.hip``,
+head dim 64 only; CPU: a plain fp32 cache, the reference of the GPU path).  The document mask is not applied there.
 """
 from __future__ import annotations
 
@@ -288,6 +292,181 @@ class GPT2(nn.Module):
         return TX.LMHeadLossFn.apply(x, targets.reshape(-1).long().contiguous(), c.eps, wte_k, tr.ln_f.weight,
                                      tr.ln_f.bias, wte, hd, ddp is not None, train,
                                      c.label_smoothing if train else 0.0, c.z_loss if train else 0.0)
+
+    # ------------------------------------------------------------------------------------------ generation
+    @staticmethod
+    def kv_cache_len(P, max_new_tokens):
+        """Tmax of the GPU cache for prompts of P columns: the prefill writes the prompt padded to a multiple of 128"""
+        return max((P + 127) // 128 * 128, P + max_new_tokens)
+
+    @staticmethod
+    def _sample(logits, temperature, top_k, generator):
+        """fp32 logits [B][V] -> token ids [B]: argmax for temperature 0 or top_k 1, else temperature, top-k, multinomial"""
+        if temperature == 0 or top_k == 1:
+            return logits.argmax(-1)
+        lg = logits / temperature
+        if top_k is not None:
+            kth = torch.topk(lg, min(int(top_k), lg.shape[-1]), dim=-1).values[:, -1:]
+            lg = lg.masked_fill(lg < kth, float("-inf"))
+        return torch.multinomial(torch.softmax(lg, -1), 1, generator=generator).squeeze(1)
+
+    @torch.no_grad()
+    def generate(self, idx, max_new_tokens, *, temperature=1.0, top_k=None, eos_token=None, prompt_lens=None,
+                 generator=None, graph=False, return_logits=False, cache=None):
+        """Sample ``max_new_tokens`` tokens after the prompts ``idx`` int [B][P] with a key/value cache: one prefill over
+        the prompt, then one single-token step per new token (GPU: ``ops.transformer.block_decode`` on the decode
+        attention kernel of ``csrc/kernels/attention_decode.hip``; CPU: plain PyTorch in fp32 with per-layer k, v lists,
+        any head dim, the numerics reference of the GPU path).  Runs under no_grad with evaluation semantics (no dropout)
+        and leaves the model as it found it.
+
+        ``prompt_lens`` int [B] (default: the full row) lets a batch mix prompt lengths: row b's prompt is
+        idx[b, :prompt_lens[b]], the rest of the row is padding.  Returns tokens int64 [B][P + max_new_tokens]: ``idx``
+        followed by the new tokens of every row in columns P.. (for a short prompt they continue idx[b, :prompt_lens[b]],
+        not the padding); with ``return_logits`` also the fp32 logits [B][max_new_tokens][V] each token was drawn from.
+
+        Sampling: ``temperature == 0`` or ``top_k == 1`` is argmax; otherwise temperature, then top-k, then
+        torch.multinomial with ``generator`` (eager torch on the step's logits, outside any captured region).  A row that
+        has emitted ``eos_token`` keeps emitting it (device-side mask; the loop always runs max_new_tokens steps and never
+        reads the device from the host).  ``graph=True`` (GPU): after one eager warm-up step one decode step is captured
+        with torch.cuda.graph on a single stream and replayed; the cache length lives on the device, so a replay follows
+        it.  ``cache`` (GPU): an ``ops.transformer.KVCache`` of this batch size with Tmax >= kv_cache_len(P,
+        max_new_tokens) to reuse; it is reset first.  ``config.doc_mask_eot`` is not applied: a prompt is one document.
+        The block linears are bf16 even with ``config.fp8``."""
+        c = self.config
+        if idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
+            raise ValueError(f"generate: idx must be [B][P] with B, P >= 1, got {tuple(idx.shape)}")
+        B, P = idx.shape
+        max_new_tokens = int(max_new_tokens)
+        if max_new_tokens < 0:
+            raise ValueError(f"generate: max_new_tokens must be >= 0, got {max_new_tokens}")
+        if prompt_lens is None:
+            pl = [P] * B
+        else:
+            pl = [int(v) for v in (prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
+            if len(pl) != B or min(pl) < 1 or max(pl) > P:
+                raise ValueError(f"generate: prompt_lens must be {B} lengths in [1, {P}], got {pl}")
+        if max(pl) + max_new_tokens > c.block_size:
+            raise ValueError(f"generate: prompt length {max(pl)} + max_new_tokens {max_new_tokens} > block size "
+                             f"{c.block_size}")
+        if temperature < 0 or (top_k is not None and int(top_k) < 1):
+            raise ValueError(f"generate: temperature must be >= 0 and top_k >= 1, got {temperature!r}, {top_k!r}")
+        hd = c.n_embd // c.n_head
+        if idx.is_cuda and hd != 64:
+            raise ValueError(f"generation needs the fused kernels (head dim 64); got head dim {hd}: the decode attention "
+                             f"kernel has no other head dim (the CPU path runs any)")
+        idx = idx.long()
+        out = torch.cat([idx, idx.new_zeros(B, max_new_tokens)], 1)
+        if max_new_tokens == 0:
+            return (out, torch.empty(B, 0, c.vocab_size, device=idx.device)) if return_logits else out
+        pl_dev = torch.tensor(pl, device=idx.device, dtype=torch.int32)
+        if idx.is_cuda:
+            logits, step = self._generate_fused(idx, pl_dev, max_new_tokens, graph, cache)
+        else:
+            logits, step = self._generate_reference(idx, pl_dev, max(pl) + max_new_tokens)
+        finished = torch.zeros(B, dtype=torch.bool, device=idx.device)
+        kept = []
+        for i in range(max_new_tokens):
+            if return_logits:
+                kept.append(logits.clone())
+            tok = self._sample(logits, temperature, top_k, generator)
+            if eos_token is not None:
+                tok = torch.where(finished, torch.full_like(tok, int(eos_token)), tok)
+                finished = finished | (tok == int(eos_token))
+            out[:, P + i] = tok
+            if i + 1 < max_new_tokens:
+                logits = step(tok)
+        return (out, torch.stack(kept, 1)) if return_logits else out
+
+    def _generate_fused(self, idx, pl_dev, max_new_tokens, graph, cache):
+        """GPU: prefill -> (fp32 logits [B][V] at each prompt's last position, step(tok) -> the next logits)"""
+        c, tr = self.config, self.transformer
+        B, P = idx.shape
+        Tp = (P + 127) // 128 * 128                  # right-padded: causality keeps the padding invisible to real positions
+        if cache is None:
+            cache = TX.KVCache(self, B, self.kv_cache_len(P, max_new_tokens), idx.device)
+        elif cache.B != B or cache.Tmax < self.kv_cache_len(P, max_new_tokens) or cache.k.device != idx.device:
+            raise ValueError(f"generate: cache of B = {cache.B}, Tmax = {cache.Tmax} on {cache.k.device} does not fit "
+                             f"B = {B}, Tmax >= {self.kv_cache_len(P, max_new_tokens)} on {idx.device}")
+        cache.reset()
+        wte_k, wpe_k = OF.weight_bf16(tr.wte.weight), OF.weight_bf16(tr.wpe.weight)
+        blocks = [blk.fused_params() for blk in tr.h]
+        lnw, lnb = tr.ln_f.weight, tr.ln_f.bias
+        last = c.block_size - 1
+        # prefill: positions past the table are clamped to its last row
+        wpe_p = wpe_k if Tp <= c.block_size else torch.cat([wpe_k, wpe_k[-1:].expand(Tp - c.block_size, -1)]).contiguous()
+        from ..ops import kernels as K
+        x = K.embedding_fwd(F.pad(idx, (0, Tp - P)).reshape(-1).contiguous(), wte_k, wpe_p, Tp)
+        for layer, (params, shadows) in enumerate(blocks):
+            x = TX.block_prefill(x, (B, Tp, c.n_head, c.eps), shadows, params, cache, layer)
+        rows = torch.arange(B, device=idx.device) * Tp + pl_dev.long() - 1
+        xf, _, _ = K.layernorm_fwd(x.index_select(0, rows), lnw, lnb, c.eps)
+        logits = TX.BL.linear_fwd(xf, wte_k).float()
+        cache.lens.copy_(pl_dev)
+        tok_buf = torch.zeros(B, dtype=torch.int64, device=idx.device)
+        logit_buf = torch.empty_like(logits)
+
+        def one_step():     # tok_buf -> logit_buf; no host read-back, no side stream: capturable as it stands
+            pos = cache.lens.long().clamp_(max=last)
+            x = (wte_k.index_select(0, tok_buf).float() + wpe_k.index_select(0, pos).float()).to(torch.bfloat16)
+            for layer, (params, shadows) in enumerate(blocks):
+                x = TX.block_decode(x, (B, 1, c.n_head, c.eps), shadows, params, cache, layer)
+            xf, _, _ = K.layernorm_fwd(x, lnw, lnb, c.eps)
+            logit_buf.copy_(TX.BL.linear_fwd(xf, wte_k))
+            cache.lens.add_(1)
+
+        state = {"n": 0, "graph": None}
+
+        def step(tok):
+            tok_buf.copy_(tok)
+            if not graph or state["n"] == 0:            # eager, and the warm-up step of graph=True
+                one_step()
+            else:
+                if state["graph"] is None:
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        one_step()
+                    state["graph"] = g
+                state["graph"].replay()
+            state["n"] += 1
+            return logit_buf
+        return logits, step
+
+    def _generate_reference(self, idx, pl_dev, Tmax):
+        """CPU (any device, plain PyTorch, fp32): the same prefill + cached steps with per-layer k, v lists"""
+        c, tr = self.config, self.transformer
+        B, P = idx.shape
+        H, hd = c.n_head, c.n_embd // c.n_head
+        dev = idx.device
+        ks = [torch.zeros(B, H, Tmax, hd, device=dev, dtype=tr.wte.weight.dtype) for _ in tr.h]
+        vs = [torch.zeros_like(k) for k in ks]
+        lens = pl_dev.long().clone()
+        ar = torch.arange(B, device=dev)
+
+        def heads(t, T):
+            return t.view(B, T, H, hd).transpose(1, 2)
+
+        x = tr.wte(idx) + tr.wpe(torch.arange(P, device=dev).clamp(max=c.block_size - 1))
+        for blk, kc, vc in zip(tr.h, ks, vs):
+            q, k, v = (heads(t, P) for t in blk.attn.c_attn(blk.ln_1(x)).split(c.n_embd, dim=2))
+            kc[:, :, :P], vc[:, :, :P] = k, v
+            y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
+            x = x + blk.attn.c_proj(y.transpose(1, 2).reshape(B, P, c.n_embd))
+            x = x + blk.mlp(blk.ln_2(x))
+        logits = self.lm_head(tr.ln_f(x[ar, lens - 1])).float()
+        keys = torch.arange(Tmax, device=dev)
+
+        def step(tok):
+            x = tr.wte(tok) + tr.wpe(lens.clamp(max=c.block_size - 1))                 # [B][D]
+            vis = (keys[None, :] <= lens[:, None])[:, None, None, :]                    # keys 0..lens[b], new one included
+            for blk, kc, vc in zip(tr.h, ks, vs):
+                q, k, v = (t.view(B, H, hd) for t in blk.attn.c_attn(blk.ln_1(x)).split(c.n_embd, dim=1))
+                kc[ar, :, lens], vc[ar, :, lens] = k, v
+                y = F.scaled_dot_product_attention(q.unsqueeze(2), kc, vc, attn_mask=vis)
+                x = x + blk.attn.c_proj(y.reshape(B, c.n_embd))
+                x = x + blk.mlp(blk.ln_2(x))
+            lens.add_(1)
+            return self.lm_head(tr.ln_f(x)).float()
+        return logits, step
 
     def _forward_reference(self, idx, targets=None, doc=None, drop=None):
         B, T = idx.shape

@@ -144,6 +144,9 @@ _SIGS = {
     "pdnn_flash_attn_doc_fwd": [P, P, P, I, I, I, F, P, P, P],
     "pdnn_flash_attn_doc_bwd": [P, P, P, P, P, P, I, I, I, F, P, P, P],
     "pdnn_doc_bounds": [P, ctypes.c_longlong, P, P, I, I, P],
+    "pdnn_attn_decode": [P, P, P, P, P, P, I, I, I, I, F, P],
+    "pdnn_attn_decode_ws": [I, I, I, I],
+    "pdnn_kv_cache_fill": [P, P, P, I, I, I, I, P],
     "pdnn_flash_attn_drop_fwd": [P, P, P, I, I, I, F, F, P, I, P, P, P],
     "pdnn_flash_attn_drop_bwd": [P, P, P, P, P, P, I, I, I, F, F, P, I, P, P, P],
     "pdnn_dropout_add_fwd": [P, P, P, L, I, F, P, I, P],

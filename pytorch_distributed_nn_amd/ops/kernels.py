@@ -1486,6 +1486,68 @@ def flash_attn_doc_bwd(qkv, out, dout, lse2, doc_start, doc_end, B, T, H, scale)
     return dqkv
 
 
+# ----------------------------------------------------------------------------------- decode attention (attention_decode.hip)
+DECODE_CHUNK = 128          # keys per block of the split; profiles/attention_decode.txt holds the sweep that picked it
+DECODE_CHUNKS = (64, 128, 256)
+
+
+def _cache_chk(name, kcache, vcache, dev):
+    for t, what in ((kcache, "kcache"), (vcache, "vcache")):
+        _chk(torch.is_tensor(t) and t.dtype == BF16 and t.is_cuda and t.dim() == 4 and t.shape[3] == 64
+             and t.is_contiguous() and t.device == dev and t.data_ptr() % 16 == 0,
+             f"{name}: {what} must be contiguous CUDA bf16 [B][H][Tmax][64] on {dev}")
+    _chk(kcache.shape == vcache.shape and min(kcache.shape) >= 1,
+         f"{name}: kcache {tuple(kcache.shape)} and vcache {tuple(vcache.shape)} must have one non-empty shape")
+
+
+def attn_decode_ws(B, H, Tmax, chunk=DECODE_CHUNK):
+    """fp32 elements of the ``part`` scratch of :func:`attn_decode`"""
+    _chk(chunk in DECODE_CHUNKS, f"attn_decode: chunk must be one of {DECODE_CHUNKS}, got {chunk!r}")
+    n = lib().pdnn_attn_decode_ws(B, H, Tmax, chunk)
+    _chk(n > 0, f"attn_decode: B={B} H={H} Tmax={Tmax} chunk={chunk}")
+    return n
+
+
+def attn_decode(qkv, kcache, vcache, lens, chunk=DECODE_CHUNK, out=None, part=None, scale=None):
+    """One new token per sequence against the cache, head dim 64: qkv bf16 [B][3*H*64] (packed as for flash_attn_fwd),
+    kcache / vcache bf16 [B][H][Tmax][64], lens int32 [B] on the device (tokens already cached; read by the kernel only).
+    Stores the new k, v rows into slot lens[b] and returns out bf16 [B][H*64] = softmax over keys 0..lens[b] times V.
+    ``lens`` is not changed.  ``out`` / ``part`` (fp32, >= attn_decode_ws elements): preallocated buffers, so that a
+    captured step allocates nothing.  ``scale`` defaults to 1 / 8."""
+    _bf16_c(qkv, "attn_decode.qkv")
+    _chk(isinstance(chunk, int) and chunk in DECODE_CHUNKS, f"attn_decode: chunk must be one of {DECODE_CHUNKS}, got {chunk!r}")
+    _cache_chk("attn_decode", kcache, vcache, qkv.device)
+    B, H, Tmax, _ = kcache.shape
+    _chk(qkv.shape == (B, 3 * H * 64), f"attn_decode: qkv {tuple(qkv.shape)} for B={B} H={H}: expected [B][3*H*64]")
+    _chk(torch.is_tensor(lens) and lens.dtype == torch.int32 and lens.shape == (B,) and lens.is_contiguous()
+         and lens.device == qkv.device, f"attn_decode: lens must be contiguous int32 [{B}] on {qkv.device}")
+    ws = attn_decode_ws(B, H, Tmax, chunk)
+    if out is None:
+        out = torch.empty(B, H * 64, device=qkv.device, dtype=BF16)
+    else:
+        _chk(out.dtype == BF16 and out.shape == (B, H * 64) and out.is_contiguous() and out.device == qkv.device,
+             f"attn_decode: out must be contiguous bf16 [{B}][{H * 64}] on {qkv.device}")
+    if part is None:
+        part = torch.empty(ws, device=qkv.device, dtype=F32)
+    else:
+        _chk(part.dtype == F32 and part.is_contiguous() and part.numel() >= ws and part.device == qkv.device,
+             f"attn_decode: part must be contiguous fp32 with >= {ws} elements on {qkv.device}")
+    call("pdnn_attn_decode", ptr(qkv), ptr(kcache), ptr(vcache), ptr(lens), ptr(out), ptr(part), B, H, Tmax, chunk,
+         float(0.125 if scale is None else scale), stream())
+    return out
+
+
+def kv_cache_fill(qkv, kcache, vcache, B, T):
+    """Prefill: the K and V columns of qkv bf16 [B*T][3*H*64] into slots 0..T-1 of kcache / vcache bf16 [B][H][Tmax][64]
+    (T <= Tmax; slots >= T are untouched)."""
+    _bf16_c(qkv, "kv_cache_fill.qkv")
+    _cache_chk("kv_cache_fill", kcache, vcache, qkv.device)
+    Bc, H, Tmax, _ = kcache.shape
+    _chk(B == Bc and 1 <= T <= Tmax and qkv.shape == (B * T, 3 * H * 64),
+         f"kv_cache_fill: qkv {tuple(qkv.shape)} B={B} T={T} for a cache {tuple(kcache.shape)}")
+    call("pdnn_kv_cache_fill", ptr(qkv), ptr(kcache), ptr(vcache), B, T, H, Tmax, stream())
+
+
 # ----------------------------------------------------------------------------------- dropout (csrc/kernels/dropout_rng.h)
 def dropout_p_eff(p):
     """The probability the kernels use for ``p``: quantised to thr / 256 (the scale is 1 / (1 - p_eff))."""

@@ -496,6 +496,70 @@ class GPT2BlockFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------
+# inference: key/value cache, prefill and single-token decode blocks (plain functions, no autograd)
+# ------------------------------------------------------------------------------------------------
+class KVCache:
+    """The key/value cache of one generation batch on the GPU (csrc/kernels/attention_decode.hip): one K and one V
+    allocation bf16 [L][B][H][Tmax][64], ``lens`` int32 [B] on the device (tokens of sequence b already cached; the
+    decode kernels read it there, the host never does) and the fp32 scratch of the split decode kernel.  Slots at or
+    past lens[b] may hold anything, so :meth:`reset` only zeroes ``lens``."""
+
+    def __init__(self, model, B, Tmax, device, chunk=None):
+        c = model.config
+        hd = c.n_embd // c.n_head
+        if hd != 64 or c.n_embd % c.n_head:
+            raise ValueError(f"generation needs the fused kernels (head dim 64); got head dim {hd}: the decode "
+                             f"attention kernel has no other head dim (the CPU path runs any)")
+        if B < 1 or Tmax < 1:
+            raise ValueError(f"KVCache: B = {B}, Tmax = {Tmax}")
+        self.B, self.H, self.Tmax, self.L = B, c.n_head, Tmax, c.n_layer
+        self.chunk = K.DECODE_CHUNK if chunk is None else chunk
+        self.k = torch.zeros(c.n_layer, B, c.n_head, Tmax, 64, device=device, dtype=BF16)
+        self.v = torch.zeros_like(self.k)
+        self.lens = torch.zeros(B, device=device, dtype=torch.int32)
+        self.part = torch.empty(K.attn_decode_ws(B, c.n_head, Tmax, self.chunk), device=device, dtype=F32)
+
+    def reset(self):
+        self.lens.zero_()
+
+
+def block_prefill(x, conf, shadows, params, cache, layer):
+    """One block over the whole (padded) prompt, the forward kernel sequence of :class:`GPT2BlockFn` with nothing saved:
+    x bf16 [B*T][D], conf = (B, T, H, eps) with T % 128 == 0 -> x2; the K and V of every position also go into slots
+    0..T-1 of ``cache`` layer ``layer``.  The linears are bf16 (BL.linear_fwd) whatever config.fp8 says."""
+    B, T, H, eps = conf[:4]
+    ln1w, ln1b, _, attn_b, _, proj_b, ln2w, ln2b, _, fc_b, _, fc2_b = params
+    wqkv, wproj, wfc, wfc2 = shadows
+    D = x.shape[1]
+    if not use_flash(T, D, H):
+        raise ValueError(f"generation needs the fused kernels (head dim 64, T % 128 == 0); got head dim {D // H}, T = {T}")
+    ln1, _, _ = K.layernorm_fwd(x, ln1w, ln1b, eps)
+    qkv = BL.linear_fwd(ln1, wqkv, bias=attn_b)
+    K.kv_cache_fill(qkv, cache.k[layer], cache.v[layer], B, T)
+    y, _ = K.flash_attn_fwd(qkv, B, T, H, 1.0 / math.sqrt(D // H))
+    x1 = BL.linear_fwd(y, wproj, bias=proj_b, res=x)
+    ln2, _, _ = K.layernorm_fwd(x1, ln2w, ln2b, eps)
+    h = BL.linear_fwd(ln2, wfc, bias=fc_b, act=2)
+    return BL.linear_fwd(h, wfc2, bias=fc2_b, res=x1)
+
+
+def block_decode(x, conf, shadows, params, cache, layer):
+    """One block on the one new token per sequence: x bf16 [B][D] -> x2, with attn_decode (which also stores the new
+    k, v into slot cache.lens[b]) in the middle.  Nothing here reads the device from the host or changes cache.lens."""
+    B, _, H, eps = conf[:4]
+    ln1w, ln1b, _, attn_b, _, proj_b, ln2w, ln2b, _, fc_b, _, fc2_b = params
+    wqkv, wproj, wfc, wfc2 = shadows
+    ln1, _, _ = K.layernorm_fwd(x, ln1w, ln1b, eps)
+    qkv = BL.linear_fwd(ln1, wqkv, bias=attn_b)
+    y = K.attn_decode(qkv, cache.k[layer], cache.v[layer], cache.lens, chunk=cache.chunk, part=cache.part,
+                      scale=1.0 / math.sqrt(x.shape[1] // H))
+    x1 = BL.linear_fwd(y, wproj, bias=proj_b, res=x)
+    ln2, _, _ = K.layernorm_fwd(x1, ln2w, ln2b, eps)
+    h = BL.linear_fwd(ln2, wfc, bias=fc_b, act=2)
+    return BL.linear_fwd(h, wfc2, bias=fc2_b, res=x1)
+
+
+# ------------------------------------------------------------------------------------------------
 # final LayerNorm + tied LM head + cross-entropy
 # ------------------------------------------------------------------------------------------------
 class LMHeadLossFn(torch.autograd.Function):
