@@ -268,6 +268,26 @@ __global__ void __launch_bounds__(NT) embedding_fwd_kernel(const int64_t* __rest
     }
 }
 
+// decode step: x[b] = bf16(float(wte[tok[b]]) + float(wpe[min(lens[b], last)])), one thread per 16 bytes
+__global__ void __launch_bounds__(NT) embedding_decode_kernel(const int64_t* __restrict__ tok,
+                                                               const int* __restrict__ lens,
+                                                               const bf16_t* __restrict__ wte,
+                                                               const bf16_t* __restrict__ wpe, bf16_t* __restrict__ out,
+                                                               int B, int D, int V, int last) {
+    const int CH = D / 8;
+    const int i = blockIdx.x * NT + threadIdx.x;
+    if (i >= B * CH) return;
+    const int b = i / CH, c = (i - b * CH) * 8;
+    const long t = min(max(tok[b], (int64_t)0), (int64_t)(V - 1));      // clamped before they become addresses
+    const int p = min(max(lens[b], 0), last);
+    float a[8], e[8];
+    unpack8(*reinterpret_cast<const u16x8_t*>(wte + t * D + c), a);
+    unpack8(*reinterpret_cast<const u16x8_t*>(wpe + (long)p * D + c), e);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a[j] += e[j];
+    *reinterpret_cast<u16x8_t*>(out + (long)b * D + c) = pack8(a);
+}
+
 // dwte[idx[r]] += sc * g[r] (fp32 atomics; rows hitting the same token accumulate), dwpe[r % T] += g[r]; either
 // table may be absent (the split tied-embedding path reduces dwpe and the wte rows separately: parallel/ddp.py)
 __global__ void __launch_bounds__(NT) embedding_bwd_kernel(const int64_t* __restrict__ idx,
@@ -333,6 +353,17 @@ PDNN_API int pdnn_embedding_fwd(const int64_t* idx, const bf16_t* wte, const bf1
                                 int T, int D, hipStream_t st) {
     hipLaunchKernelGGL(embedding_fwd_kernel, dim3(stream_grid((long)rows * (D / 8), NT)), dim3(NT), 0, st, idx, wte,
                        wpe, out, rows, T, D);
+    PDNN_LAUNCH_RET;
+}
+
+// decode gather: tok int64 [B], lens int32 [B], wte bf16 [V][D], wpe bf16 [last + 1][D], x_out bf16 [B][D]
+PDNN_API int pdnn_embedding_decode(const int64_t* tok, const int* lens, const bf16_t* wte, const bf16_t* wpe,
+                                   bf16_t* x_out, int B, int D, int V, int last, hipStream_t st) {
+    if (!tok || !lens || !wte || !wpe || !x_out || B < 1 || D < 8 || D % 8 || V < 1 || last < 0 ||
+        (long)B * (D / 8) > 0x7fffffffL)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(embedding_decode_kernel, dim3((unsigned)cdiv((long)B * (D / 8), NT)), dim3(NT), 0, st, tok,
+                       lens, wte, wpe, x_out, B, D, V, last);
     PDNN_LAUNCH_RET;
 }
 

@@ -391,7 +391,6 @@ class GPT2(nn.Module):
         wte_k, wpe_k = OF.weight_bf16(tr.wte.weight), OF.weight_bf16(tr.wpe.weight)
         blocks = [blk.fused_params() for blk in tr.h]
         lnw, lnb = tr.ln_f.weight, tr.ln_f.bias
-        last = c.block_size - 1
         # prefill: positions past the table are clamped to its last row
         wpe_p = wpe_k if Tp <= c.block_size else torch.cat([wpe_k, wpe_k[-1:].expand(Tp - c.block_size, -1)]).contiguous()
         from ..ops import kernels as K
@@ -400,18 +399,17 @@ class GPT2(nn.Module):
             x = TX.block_prefill(x, (B, Tp, c.n_head, c.eps), shadows, params, cache, layer)
         rows = torch.arange(B, device=idx.device) * Tp + pl_dev.long() - 1
         xf, _, _ = K.layernorm_fwd(x.index_select(0, rows), lnw, lnb, c.eps)
-        logits = TX.BL.linear_fwd(xf, wte_k).float()
+        logits = TX.BL.linear_fwd_decode(xf, wte_k).float()
         cache.lens.copy_(pl_dev)
         tok_buf = torch.zeros(B, dtype=torch.int64, device=idx.device)
         logit_buf = torch.empty_like(logits)
 
         def one_step():     # tok_buf -> logit_buf; no host read-back, no side stream: capturable as it stands
-            pos = cache.lens.long().clamp_(max=last)
-            x = (wte_k.index_select(0, tok_buf).float() + wpe_k.index_select(0, pos).float()).to(torch.bfloat16)
+            x = K.embedding_decode(tok_buf, cache.lens, wte_k, wpe_k)     # position min(lens[b], block_size - 1)
             for layer, (params, shadows) in enumerate(blocks):
                 x = TX.block_decode(x, (B, 1, c.n_head, c.eps), shadows, params, cache, layer)
             xf, _, _ = K.layernorm_fwd(x, lnw, lnb, c.eps)
-            logit_buf.copy_(TX.BL.linear_fwd(xf, wte_k))
+            logit_buf.copy_(TX.BL.linear_fwd_decode(xf, wte_k))
             cache.lens.add_(1)
 
         state = {"n": 0, "graph": None}

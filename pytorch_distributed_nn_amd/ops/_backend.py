@@ -134,6 +134,8 @@ _SIGS = {
     "pdnn_colsum_splits": [L],
     "pdnn_gemm_batched": [I, I, I, P, L, L, L, P, L, L, L, P, L, L, L, I, I, I, I, I, F, P, I, P],
     "pdnn_gemm_nt_ex": [P, L, P, L, P, L, I, I, I, F, P, I, P, P, P, I, P],
+    "pdnn_gemm_skinny": [P, L, P, P, L, I, I, I, P, I, P, P],
+    "pdnn_gemm_skinny_plan": [I, I],
     "pdnn_layernorm_fwd": [P, P, P, P, P, P, I, I, F, P],
     "pdnn_layernorm_bwd_blocks": [I],
     "pdnn_layernorm_bwd": [P, P, P, P, P, P, P, P, I, I, I, P],
@@ -154,6 +156,7 @@ _SIGS = {
     "pdnn_dropout_mask_rows": [P, L, I, F, P, I, P],
     "pdnn_dropout_mask_attn": [P, I, I, I, F, P, I, P],
     "pdnn_embedding_fwd": [P, P, P, P, I, I, I, P],
+    "pdnn_embedding_decode": [P, P, P, P, P, I, I, I, I, P],
     "pdnn_embedding_bwd": [P, P, P, P, I, I, I, P],
     "pdnn_embedding_bwd_scaled": [P, P, P, P, I, I, I, F, P],
     "pdnn_gemm_fp8": [P, L, P, L, P, L, I, I, I, P, P, I, P, P, P, I, P],

@@ -1353,6 +1353,40 @@ def gemm_nt_ex(x, w, bias=None, act=0, aux=None, res=None, dgelu=None, w_kn=Fals
     return out
 
 
+SKINNY_MAX_M = 8            # largest M of {1, .., 64} up to which gemm_skinny beat gemm_nt_ex on all five GPT-2 small
+                            # linears (profiles/gemm_skinny.txt, section 2: the LM head turns at M = 16)
+SKINNY_ROWS = 64            # rows csrc/kernels/gemm_skinny.hip takes at all
+
+
+def gemm_skinny(x, w, bias=None, act=0, res=None, out=None):
+    """y = act(x @ w^T + bias) (+res) for 1 <= M <= 64 rows on the weight-streaming kernel (csrc/kernels/gemm_skinny.hip):
+    x bf16 [M][K] (row-strided), w bf16 [N][K] contiguous, bias fp32 [N], act 0 / 2 = none / GELU(tanh), res and out bf16
+    [M][N] with one row stride.  Row b of the result does not depend on M or on the other rows."""
+    for t, nm in ((x, "x"), (w, "w")):
+        _chk(torch.is_tensor(t) and t.dtype == BF16 and t.is_cuda and t.dim() == 2 and t.data_ptr() % 16 == 0,
+             f"gemm_skinny: {nm} must be a 16-byte aligned 2-D CUDA bf16 tensor")
+    M, K = x.shape
+    N = w.shape[0]
+    _chk(1 <= M <= SKINNY_ROWS, f"gemm_skinny: 1 <= M <= {SKINNY_ROWS}, got M = {M}")
+    _chk(w.shape[1] == K and K >= 8 and N >= 8 and K % 8 == 0 and N % 8 == 0, f"gemm_skinny: {tuple(x.shape)} {tuple(w.shape)}")
+    _chk(w.is_contiguous() and w.device == x.device, "gemm_skinny: w must be contiguous [N][K] on x's device")
+    _chk(x.stride(1) == 1 and x.stride(0) >= K and x.stride(0) % 8 == 0, "gemm_skinny: x rows contiguous, row stride % 8 == 0")
+    _chk(act in (0, 2), f"gemm_skinny: act must be 0 or 2 (GELU), got {act!r}")
+    _chk(bias is None or (bias.dtype == F32 and bias.shape == (N,) and bias.is_contiguous()
+                          and bias.device == x.device), f"gemm_skinny: bias must be contiguous fp32 [{N}]")
+    if out is None:
+        out = torch.empty(M, N, device=x.device, dtype=BF16)
+    _chk(out.dtype == BF16 and out.shape == (M, N) and out.device == x.device and out.stride(1) == 1
+         and out.stride(0) >= N and out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0,
+         f"gemm_skinny: out must be bf16 [{M}][{N}], rows contiguous, row stride % 8 == 0")
+    _chk(res is None or (res.dtype == BF16 and res.device == x.device and res.shape == out.shape
+                         and res.stride() == out.stride() and res.data_ptr() % 16 == 0),
+         "gemm_skinny: res must be bf16 of out's shape and strides")
+    call("pdnn_gemm_skinny", ptr(x), x.stride(0), ptr(w), ptr(out), out.stride(0), M, N, K, ptr(bias), int(act), ptr(res),
+         stream())
+    return out
+
+
 def layernorm_fwd(x, g, b, eps):
     _bf16_c(x, "layernorm.x")
     _chk(x.dim() == 2, "layernorm: x must be 2-D")
@@ -1668,6 +1702,28 @@ def embedding_fwd(idx, wte, wpe, T):
     _chk(wpe is None or (wpe.shape[1] == D and wpe.shape[0] >= T), "embedding: wpe shape")
     out = torch.empty(R, D, device=wte.device, dtype=BF16)
     call("pdnn_embedding_fwd", ptr(idx), ptr(wte), ptr(wpe), ptr(out), R, T, D, stream())
+    return out
+
+
+def embedding_decode(tok, lens, wte, wpe, out=None):
+    """Decode step gather, one launch: out[b] = bf16(float(wte[tok[b]]) + float(wpe[min(lens[b], last)])), last =
+    wpe.shape[0] - 1.  tok int64 [B], lens int32 [B] (device; both clamped into their tables by the kernel)."""
+    _bf16_c(wte, "embedding_decode.wte")
+    _bf16_c(wpe, "embedding_decode.wpe")
+    _chk(wte.dim() == 2 and wpe.dim() == 2 and wpe.shape[1] == wte.shape[1] and wte.shape[1] % 8 == 0
+         and wte.shape[1] >= 8 and wpe.device == wte.device, "embedding_decode: wte [V][D], wpe [P][D], D % 8 == 0")
+    _chk(torch.is_tensor(tok) and tok.dtype == torch.int64 and tok.dim() == 1 and tok.numel() >= 1 and tok.is_contiguous()
+         and tok.device == wte.device, "embedding_decode: tok must be contiguous int64 [B] on wte's device")
+    B, D = tok.numel(), wte.shape[1]
+    _chk(torch.is_tensor(lens) and lens.dtype == torch.int32 and lens.shape == (B,) and lens.is_contiguous()
+         and lens.device == wte.device, f"embedding_decode: lens must be contiguous int32 [{B}] on wte's device")
+    if out is None:
+        out = torch.empty(B, D, device=wte.device, dtype=BF16)
+    else:
+        _bf16_c(out, "embedding_decode.out")
+        _chk(out.shape == (B, D) and out.device == wte.device, f"embedding_decode: out must be bf16 [{B}][{D}]")
+    call("pdnn_embedding_decode", ptr(tok), ptr(lens), ptr(wte), ptr(wpe), ptr(out), B, D, wte.shape[0], wpe.shape[0] - 1,
+         stream())
     return out
 
 

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import torch
 
+from .. import tuning as _tuning
 from . import kernels as K
 from .functional import weight_bf16_t
 
@@ -30,6 +31,15 @@ def linear_fwd(x, wk, bias=None, act=0, aux=None, res=None):
     """y = act(x @ wk^T + bias) (+ res), bf16 [M][N]; with act == 2 (GELU) ``aux`` receives the
     pre-activation.  Same contract as :func:`kernels.gemm_nt_ex`."""
     return K.gemm_nt_ex(x, wk, bias=bias, act=act, aux=aux, res=res)
+
+
+def linear_fwd_decode(x, wk, bias=None, act=0, res=None):
+    """:func:`linear_fwd` for the M = B rows of a decode step: up to ``kernels.SKINNY_MAX_M`` rows run the
+    weight-streaming kernel (``kernels.gemm_skinny``, csrc/kernels/gemm_skinny.hip) unless tuning ``decode_skinny``
+    is 0; everything else is :func:`linear_fwd`."""
+    if _tuning.get("decode_skinny") and x.is_cuda and x.shape[0] <= K.SKINNY_MAX_M:
+        return K.gemm_skinny(x, wk, bias=bias, act=act, res=res)
+    return linear_fwd(x, wk, bias=bias, act=act, res=res)
 
 
 def linear_dgrad(g, wk, dgelu=None, p=None):

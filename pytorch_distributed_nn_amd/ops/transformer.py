@@ -545,18 +545,19 @@ def block_prefill(x, conf, shadows, params, cache, layer):
 
 def block_decode(x, conf, shadows, params, cache, layer):
     """One block on the one new token per sequence: x bf16 [B][D] -> x2, with attn_decode (which also stores the new
-    k, v into slot cache.lens[b]) in the middle.  Nothing here reads the device from the host or changes cache.lens."""
+    k, v into slot cache.lens[b]) in the middle; the four linears have M = B rows (BL.linear_fwd_decode).  Nothing here
+    reads the device from the host or changes cache.lens."""
     B, _, H, eps = conf[:4]
     ln1w, ln1b, _, attn_b, _, proj_b, ln2w, ln2b, _, fc_b, _, fc2_b = params
     wqkv, wproj, wfc, wfc2 = shadows
     ln1, _, _ = K.layernorm_fwd(x, ln1w, ln1b, eps)
-    qkv = BL.linear_fwd(ln1, wqkv, bias=attn_b)
+    qkv = BL.linear_fwd_decode(ln1, wqkv, bias=attn_b)
     y = K.attn_decode(qkv, cache.k[layer], cache.v[layer], cache.lens, chunk=cache.chunk, part=cache.part,
                       scale=1.0 / math.sqrt(x.shape[1] // H))
-    x1 = BL.linear_fwd(y, wproj, bias=proj_b, res=x)
+    x1 = BL.linear_fwd_decode(y, wproj, bias=proj_b, res=x)
     ln2, _, _ = K.layernorm_fwd(x1, ln2w, ln2b, eps)
-    h = BL.linear_fwd(ln2, wfc, bias=fc_b, act=2)
-    return BL.linear_fwd(h, wfc2, bias=fc2_b, res=x1)
+    h = BL.linear_fwd_decode(ln2, wfc, bias=fc_b, act=2)
+    return BL.linear_fwd_decode(h, wfc2, bias=fc2_b, res=x1)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -38,6 +38,9 @@ wgrad_plan_cus     128      CUs the tile-width / K-split plan of a GPT-2 weight 
                             the whole chip
 xent_fused         1        GPT-2 training forward writes the unscaled cross-entropy gradient over the logits in the same
                             pass (ops/transformer.py LMHeadLossFn; 0: separate forward and backward passes)
+decode_skinny      1        GPT-2 decode linears (M = batch rows, up to ops.kernels.SKINNY_MAX_M) on the weight-streaming
+                            skinny-M kernel (csrc/kernels/gemm_skinny.hip; profiles/gemm_skinny.txt); 0 = the training
+                            GEMM engines, bit for bit the path before that kernel
 ds_sub             1        stride-2 1x1 shortcut convs read a contiguous copy of their input's even pixels (one
                             subsample pass): the forward then runs as a stride-1 1x1 conv, the weight gradient as a
                             plain GEMM on the ping-pong engine (0: the implicit-GEMM engine's strided gathers)
@@ -63,7 +66,7 @@ from __future__ import annotations
 
 import os
 
-DEFAULTS = {"side_wgrad": 1, "wide1x1_dgrad": 1, "a2_fold": 1, "wt_prefetch": 0, "wt_layer_batch": 1, "colsum_atomic": 1, "bias_in_wgrad": 1, "s2_halo": 3, "ds_sub": 1, "wgrad1x1_pp_pix": 200704, "gpt2_side_wgrad": 1, "xent_fused": 1, "wgrad_plan_cus": 128}
+DEFAULTS = {"side_wgrad": 1, "wide1x1_dgrad": 1, "a2_fold": 1, "wt_prefetch": 0, "wt_layer_batch": 1, "colsum_atomic": 1, "bias_in_wgrad": 1, "s2_halo": 3, "ds_sub": 1, "wgrad1x1_pp_pix": 200704, "gpt2_side_wgrad": 1, "xent_fused": 1, "wgrad_plan_cus": 128, "decode_skinny": 1}
 
 _VALUES = dict(DEFAULTS)
 

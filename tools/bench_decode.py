@@ -7,8 +7,19 @@
      full forward (padded to 128) per token;
   3. the share of one eager decode step spent in the M = B linears (the case for a skinny-M GEMM).
 
+With --skinny (the record behind ops.kernels.SKINNY_MAX_M, profiles/gemm_skinny.txt) instead:
+
+  1. gemm_skinny against gemm_nt_ex (the path before it) on the five linears of GPT-2 small with their real epilogues,
+     M in {1, 2, 4, 8, 16, 32, 64}: us per call and GB/s over the weight bytes.  A call is timed inside a captured graph
+     of back-to-back calls that rotate over enough copies of the weight to exceed the 256 MiB Infinity Cache, so the
+     weights come from HBM as in a decode step and the figure includes the kernel boundary, not the host's launch cost;
+  2. the largest M of that list up to which the skinny kernel is faster on all five shapes (SKINNY_MAX_M);
+  3. the model section at tuning decode_skinny = 1 and = 0 (0 is the path before the kernel, bit for bit: a same-process
+     A/B), and the linears' share of the eager step at both.
+
 One process, warm-up first, many iterations, medians of per-iteration event timings.  Nothing here is a pass/fail gate.
-    python tools/bench_decode.py [--out profiles/attention_decode.txt] [--iters 200] [--tokens 64]"""
+    python tools/bench_decode.py [--out profiles/attention_decode.txt] [--iters 200] [--tokens 64]
+    python tools/bench_decode.py --skinny [--out profiles/gemm_skinny.txt]"""
 import argparse
 import os
 import statistics
@@ -58,6 +69,108 @@ def bench_kernel(lines, iters):
     lines.append(f"fastest chunk per (B, lens): {dict((k, min(v)[1]) for k, v in best.items())}")
     lines.append("sum over (B, lens) of time / best time: " + ", ".join(f"chunk {c}: {r:.3f}" for c, r in rel.items()))
     lines.append(f"chosen chunk: {pick}; ops.kernels.DECODE_CHUNK = {K.DECODE_CHUNK}")
+    lines.append("")
+
+
+SKINNY_SHAPES = [("qkv", 2304, 768, dict(bias=True)), ("proj", 768, 768, dict(bias=True, res=True)),
+                 ("fc", 3072, 768, dict(bias=True, act=2)), ("fc2", 768, 3072, dict(bias=True, res=True)),
+                 ("lm_head", 50304, 768, dict())]
+SKINNY_MS = [1, 2, 4, 8, 16, 32, 64]
+HBM_GBS, BOUNDARY_US = 6300.0, (1.2, 1.45)            # the achievable HBM rate and the kernel-boundary floor
+
+
+def graph_us(calls, reps, warm):
+    """median us per call of a captured graph of ``calls`` (a list of thunks, run back to back on one stream)"""
+    for f in calls[:4]:
+        f()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for f in calls:
+            f()
+    return timed(g.replay, reps, warm) * 1e3 / len(calls)
+
+
+def bench_skinny(lines, reps):
+    from pytorch_distributed_nn_amd.ops import kernels as K
+    bf = torch.bfloat16
+    lines.append("1. gemm_skinny vs gemm_nt_ex, the five linears of GPT-2 small with their epilogues; us per call inside a")
+    lines.append("   captured graph of calls rotating over > 256 MiB of weight copies (HBM-resident weights, boundary included;")
+    lines.append(f"   median of {reps} replays); GB/s over the weight bytes.  For scale: {HBM_GBS / 1e3:.1f} TB/s achievable HBM rate,")
+    lines.append(f"   {BOUNDARY_US[0]}-{BOUNDARY_US[1]} us kernel-boundary floor per call.")
+    lines.append("   shape      N      K    M   skinny us   GB/s   nt_ex us   GB/s   speed-up   floor us (bytes / 6.3 TB/s)")
+    faster = {M: True for M in SKINNY_MS}
+    for name, N, Kd, ep in SKINNY_SHAPES:
+        nbytes = 2 * N * Kd
+        ncopy = max(2, -(-320 * 2 ** 20 // nbytes))
+        ws = [(torch.randn(N, Kd, device="cuda") * 0.02).to(bf) for _ in range(ncopy)]
+        bias = torch.randn(N, device="cuda") if ep.get("bias") else None
+        for M in SKINNY_MS:
+            x = torch.randn(M, Kd, device="cuda").to(bf)
+            res = torch.randn(M, N, device="cuda").to(bf) if ep.get("res") else None
+            out = torch.empty(M, N, device="cuda", dtype=bf)
+            act = ep.get("act", 0)
+            t = {}
+            for kind, fn in (("skinny", K.gemm_skinny), ("nt_ex", K.gemm_nt_ex)):
+                calls = [(lambda w=w, fn=fn: fn(x, w, bias=bias, act=act, res=res, out=out)) for w in ws]
+                t[kind] = graph_us(calls, reps, 3)
+            faster[M] = faster[M] and t["skinny"] < t["nt_ex"]
+            lines.append(f"   {name:8s} {N:5d}  {Kd:5d}  {M:3d}   {t['skinny']:9.2f}  {nbytes / t['skinny'] / 1e3:5.0f}   "
+                         f"{t['nt_ex']:8.2f}  {nbytes / t['nt_ex'] / 1e3:5.0f}   {t['nt_ex'] / t['skinny']:7.2f}x   "
+                         f"{nbytes / HBM_GBS / 1e3:6.2f}")
+        del ws
+    lines.append("")
+    pick = 0
+    for M in SKINNY_MS:
+        if not faster[M]:
+            break
+        pick = M
+    lines.append("2. skinny faster than gemm_nt_ex on all five shapes: " + ", ".join(f"M={M}: {'yes' if faster[M] else 'no'}" for M in SKINNY_MS))
+    lines.append(f"   largest M up to which it is faster on all five: {pick}; ops.kernels.SKINNY_MAX_M = {K.SKINNY_MAX_M}")
+    lines.append("")
+
+
+def bench_model_ab(lines, tokens):
+    """the model section at decode_skinny = 1 and 0 (0 = the path before gemm_skinny, bit for bit)"""
+    from pytorch_distributed_nn_amd import tuning
+    from pytorch_distributed_nn_amd.models.gpt2 import build_gpt2
+    from pytorch_distributed_nn_amd.ops import functional as OF
+    from pytorch_distributed_nn_amd.ops import linear as BL
+    torch.manual_seed(0)
+    m = build_gpt2("gpt2_small").cuda().eval()
+    P = 128
+    lines.append(f"3. GPT-2 small, prompt {P}, {tokens} new tokens, greedy; ms per token = whole call / tokens, median of 5 calls;")
+    lines.append("   decode_skinny = 0 is the path before the kernel (same process, same box)")
+    lines.append("   B   decode_skinny   cached eager   cached graph   graph / eager   linears alone (eager)   share of eager step")
+    old = tuning.get("decode_skinny")
+    res = {}
+    for B in (1, 8):
+        idx = torch.randint(0, 50257, (B, P), device="cuda")
+        params, sh = m.transformer.h[0].fused_params()
+        wte = OF.weight_bf16(m.transformer.wte.weight)
+        x = torch.randn(B, 768, device="cuda").to(torch.bfloat16)
+        h = torch.randn(B, 3072, device="cuda").to(torch.bfloat16)
+
+        def gemms():
+            for _ in range(12):
+                BL.linear_fwd_decode(x, sh[0], bias=params[3])
+                BL.linear_fwd_decode(x, sh[1], bias=params[5], res=x)
+                BL.linear_fwd_decode(x, sh[2], bias=params[9], act=2)
+                BL.linear_fwd_decode(h, sh[3], bias=params[11], res=x)
+            BL.linear_fwd_decode(x, wte)
+        for v in (1, 0, 1, 0):                                     # interleaved rounds; the second round is reported too
+            tuning.set("decode_skinny", v)
+            e = timed(lambda: m.generate(idx, tokens, temperature=0.0), 5, 1) / tokens
+            g = timed(lambda: m.generate(idx, tokens, temperature=0.0, graph=True), 5, 1) / tokens
+            lin = timed(gemms, 20, 5)
+            res.setdefault((B, v), []).append((e, g))
+            lines.append(f"  {B:2d}   {v:13d}   {e:12.3f}   {g:12.3f}   {g / e:13.2f}   {lin:21.3f}   {100 * lin / e:18.0f}%")
+    tuning.set("decode_skinny", old)
+    for B in (1, 8):
+        e1, g1 = (min(r[i] for r in res[(B, 1)]) for i in (0, 1))
+        e0, g0 = (min(r[i] for r in res[(B, 0)]) for i in (0, 1))
+        lines.append(f"   B = {B}: eager {e0:.3f} -> {e1:.3f} ms / token ({e0 / e1:.2f}x), graph {g0:.3f} -> {g1:.3f} ({g0 / g1:.2f}x); "
+                     f"graph=True vs eager with the kernel: {e1 / g1:.2f}x")
     lines.append("")
 
 
@@ -118,12 +231,18 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--tokens", type=int, default=64)
     ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--skinny", action="store_true", help="the gemm_skinny sections (profiles/gemm_skinny.txt)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_decode needs a GPU"
-    lines = [f"tools/bench_decode.py on {torch.cuda.get_device_name(0)}", ""]
-    bench_kernel(lines, a.iters)
-    if not a.skip_model:
-        bench_model(lines, a.tokens)
+    lines = [f"tools/bench_decode.py{' --skinny' if a.skinny else ''} on {torch.cuda.get_device_name(0)}", ""]
+    if a.skinny:
+        bench_skinny(lines, min(a.iters, 30))
+        if not a.skip_model:
+            bench_model_ab(lines, a.tokens)
+    else:
+        bench_kernel(lines, a.iters)
+        if not a.skip_model:
+            bench_model(lines, a.tokens)
     text = "\n".join(lines)
     print(text)
     if a.out:
