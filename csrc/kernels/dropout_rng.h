@@ -7,7 +7,7 @@
 //   state    int64[2] in device memory: (seed, step).  A kernel reads it from memory, so a captured step sees the values
 //            of the replay, not of the capture.
 //   site     uint32: which dropout of the model.  layer * 4 + 0 attention probabilities, + 1 attention-branch residual,
-//            + 2 MLP-branch residual; 0x7fffffff the embedding.
+//            + 2 MLP-branch residual; 0x7fffffff the embedding; 0x7ffffffe the token draw of sample.hip (stream = row).
 //   stream   uint32: b * H + h for attention, 0 for a row op.
 //   key      z = mix64(seed + 0x9E3779B97F4A7C15 * (step + 1));  z = mix64(z ^ (site << 32 | stream));
 //            k0 = low 32 bits of z, k1 = high 32 bits;  mix64 is the splitmix64 finaliser
@@ -43,6 +43,7 @@
 
 namespace pdrop {
 constexpr uint32_t SITE_EMBD = 0x7fffffffu;
+constexpr uint32_t SITE_SAMPLE = 0x7ffffffeu;
 
 struct Key {
     uint32_t k0, k1;

@@ -300,19 +300,25 @@ class GPT2(nn.Module):
         return max((P + 127) // 128 * 128, P + max_new_tokens)
 
     @staticmethod
-    def _sample(logits, temperature, top_k, generator):
-        """fp32 logits [B][V] -> token ids [B]: argmax for temperature 0 or top_k 1, else temperature, top-k, multinomial"""
+    def _sample(logits, temperature, top_k, generator, top_p=None):
+        """fp32 logits [B][V] -> token ids [B]: argmax for temperature 0 or top_k 1, else temperature, top-k, top-p (a
+        sort: the smallest set of the most probable tokens whose mass reaches top_p), multinomial"""
         if temperature == 0 or top_k == 1:
             return logits.argmax(-1)
         lg = logits / temperature
         if top_k is not None:
             kth = torch.topk(lg, min(int(top_k), lg.shape[-1]), dim=-1).values[:, -1:]
             lg = lg.masked_fill(lg < kth, float("-inf"))
+        if top_p is not None and top_p < 1:
+            sl, si = torch.sort(lg, dim=-1, descending=True)
+            sp = torch.softmax(sl, -1)
+            drop = sp.cumsum(-1) - sp >= top_p                     # the mass before a token already reaches top_p
+            lg = lg.masked_fill(torch.zeros_like(drop).scatter_(-1, si, drop), float("-inf"))
         return torch.multinomial(torch.softmax(lg, -1), 1, generator=generator).squeeze(1)
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, *, temperature=1.0, top_k=None, eos_token=None, prompt_lens=None,
-                 generator=None, graph=False, return_logits=False, cache=None):
+                 generator=None, graph=False, return_logits=False, cache=None, top_p=None, sampler="torch", seed=None):
         """Sample ``max_new_tokens`` tokens after the prompts ``idx`` int [B][P] with a key/value cache: one prefill over
         the prompt, then one single-token step per new token (GPU: ``ops.transformer.block_decode`` on the decode
         attention kernel of ``csrc/kernels/attention_decode.hip``; CPU: plain PyTorch in fp32 with per-layer k, v lists,
@@ -331,7 +337,14 @@ class GPT2(nn.Module):
         with torch.cuda.graph on a single stream and replayed; the cache length lives on the device, so a replay follows
         it.  ``cache`` (GPU): an ``ops.transformer.KVCache`` of this batch size with Tmax >= kv_cache_len(P,
         max_new_tokens) to reuse; it is reset first.  ``config.doc_mask_eot`` is not applied: a prompt is one document.
-        The block linears are bf16 even with ``config.fp8``."""
+        The block linears are bf16 even with ``config.fp8``.
+
+        ``top_p`` (both samplers): nucleus sampling after top-k.  ``sampler="device"`` draws with the counter-based
+        generator instead of ``generator``: step i of row b uses u(``seed``, i, b), and the token is the one defined in
+        the header of ``csrc/kernels/sample.hip`` (GPU: that kernel, on the step's bf16 logits, writing the token, the
+        output column and the eos flags on the device; CPU: ``ops.sampling.sample_reference`` on the fp32 logits).  The
+        tokens are reproducible from ``seed``.  With ``graph=True`` the kernel is part of the captured step (sample ->
+        embedding -> blocks -> ln_f -> LM head -> lens += 1, step += 1): the loop issues one replay per token."""
         c = self.config
         if idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
             raise ValueError(f"generate: idx must be [B][P] with B, P >= 1, got {tuple(idx.shape)}")
@@ -350,6 +363,12 @@ class GPT2(nn.Module):
                              f"{c.block_size}")
         if temperature < 0 or (top_k is not None and int(top_k) < 1):
             raise ValueError(f"generate: temperature must be >= 0 and top_k >= 1, got {temperature!r}, {top_k!r}")
+        if top_p is not None and not float(top_p) > 0:
+            raise ValueError(f"generate: top_p must be > 0, got {top_p!r}")
+        if sampler not in ("torch", "device"):
+            raise ValueError(f"generate: sampler must be 'torch' or 'device', got {sampler!r}")
+        if sampler == "device" and (generator is not None or seed is None):
+            raise ValueError("generate: sampler='device' draws from seed: pass seed, and no generator")
         hd = c.n_embd // c.n_head
         if idx.is_cuda and hd != 64:
             raise ValueError(f"generation needs the fused kernels (head dim 64); got head dim {hd}: the decode attention "
@@ -359,6 +378,25 @@ class GPT2(nn.Module):
         if max_new_tokens == 0:
             return (out, torch.empty(B, 0, c.vocab_size, device=idx.device)) if return_logits else out
         pl_dev = torch.tensor(pl, device=idx.device, dtype=torch.int32)
+        if sampler == "device":
+            draw = dict(temperature=float(temperature), top_k=top_k, top_p=top_p, eos_token=eos_token)
+            seed = int(seed) & ((1 << 63) - 1)
+            if idx.is_cuda:
+                kept = self._generate_fused(idx, pl_dev, max_new_tokens, graph, cache,
+                                            device_sampler=(out, draw, seed, return_logits))
+                return (out, kept) if return_logits else out
+            from ..ops.sampling import sample_reference
+            logits, step = self._generate_reference(idx, pl_dev, max(pl) + max_new_tokens)
+            finished = torch.zeros(B, dtype=torch.uint8) if eos_token is not None else None
+            kept = []
+            for i in range(max_new_tokens):
+                if return_logits:
+                    kept.append(logits.clone())
+                tok, _, _ = sample_reference(logits, state=(seed, i), finished=finished, **draw)
+                out[:, P + i] = tok
+                if i + 1 < max_new_tokens:
+                    logits = step(tok)
+            return (out, torch.stack(kept, 1)) if return_logits else out
         if idx.is_cuda:
             logits, step = self._generate_fused(idx, pl_dev, max_new_tokens, graph, cache)
         else:
@@ -368,7 +406,7 @@ class GPT2(nn.Module):
         for i in range(max_new_tokens):
             if return_logits:
                 kept.append(logits.clone())
-            tok = self._sample(logits, temperature, top_k, generator)
+            tok = self._sample(logits, temperature, top_k, generator, top_p)
             if eos_token is not None:
                 tok = torch.where(finished, torch.full_like(tok, int(eos_token)), tok)
                 finished = finished | (tok == int(eos_token))
@@ -377,8 +415,10 @@ class GPT2(nn.Module):
                 logits = step(tok)
         return (out, torch.stack(kept, 1)) if return_logits else out
 
-    def _generate_fused(self, idx, pl_dev, max_new_tokens, graph, cache):
-        """GPU: prefill -> (fp32 logits [B][V] at each prompt's last position, step(tok) -> the next logits)"""
+    def _generate_fused(self, idx, pl_dev, max_new_tokens, graph, cache, device_sampler=None):
+        """GPU: prefill -> (fp32 logits [B][V] at each prompt's last position, step(tok) -> the next logits).  With
+        ``device_sampler`` = (out, draw arguments, seed, return_logits) the whole loop runs here on the sampling kernel
+        and the result is the kept fp32 logits [B][N][V] (or None)."""
         c, tr = self.config, self.transformer
         B, P = idx.shape
         Tp = (P + 127) // 128 * 128                  # right-padded: causality keeps the padding invisible to real positions
@@ -399,9 +439,13 @@ class GPT2(nn.Module):
             x = TX.block_prefill(x, (B, Tp, c.n_head, c.eps), shadows, params, cache, layer)
         rows = torch.arange(B, device=idx.device) * Tp + pl_dev.long() - 1
         xf, _, _ = K.layernorm_fwd(x.index_select(0, rows), lnw, lnb, c.eps)
-        logits = TX.BL.linear_fwd_decode(xf, wte_k).float()
+        logits16 = TX.BL.linear_fwd_decode(xf, wte_k)
         cache.lens.copy_(pl_dev)
         tok_buf = torch.zeros(B, dtype=torch.int64, device=idx.device)
+        if device_sampler is not None:
+            return self._decode_loop_device(logits16, tok_buf, cache, wte_k, wpe_k, blocks, P, max_new_tokens, graph,
+                                            *device_sampler)
+        logits = logits16.float()
         logit_buf = torch.empty_like(logits)
 
         def one_step():     # tok_buf -> logit_buf; no host read-back, no side stream: capturable as it stands
@@ -428,6 +472,50 @@ class GPT2(nn.Module):
             state["n"] += 1
             return logit_buf
         return logits, step
+
+    def _decode_loop_device(self, logit_buf, tok_buf, cache, wte_k, wpe_k, blocks, P, N, graph, out, draw, seed, keep):
+        """The decode loop with the sampling kernel inside the step.  One unit: sample from the bf16 ``logit_buf`` into
+        ``tok_buf``, column P + step of ``out`` and the eos flags; embedding -> blocks -> ln_f -> LM head into
+        ``logit_buf``; lens += 1, step += 1.  Nothing is read back and nothing runs on a side stream, so the unit is
+        capturable as it stands; the last token needs no forward and is sampled alone."""
+        from ..ops import kernels as K
+        c, tr = self.config, self.transformer
+        B, dev = tok_buf.numel(), tok_buf.device
+        lnw, lnb = tr.ln_f.weight, tr.ln_f.bias
+        state = torch.tensor([seed, 0], dtype=torch.int64, device=dev)
+        one = torch.tensor([0, 1], dtype=torch.int64, device=dev)
+        eos = draw["eos_token"]
+        finished = torch.zeros(B, dtype=torch.uint8, device=dev) if eos is not None else None
+
+        def sample():
+            K.sample_logits(logit_buf, tok_buf, state, temperature=draw["temperature"], top_k=draw["top_k"],
+                            top_p=draw["top_p"], history=out, col0=P, finished=finished, eos_token=eos)
+
+        def unit():
+            sample()
+            x = K.embedding_decode(tok_buf, cache.lens, wte_k, wpe_k)
+            for layer, (params, shadows) in enumerate(blocks):
+                x = TX.block_decode(x, (B, 1, c.n_head, c.eps), shadows, params, cache, layer)
+            xf, _, _ = K.layernorm_fwd(x, lnw, lnb, c.eps)
+            logit_buf.copy_(TX.BL.linear_fwd_decode(xf, wte_k))
+            cache.lens.add_(1)
+            state.add_(one)
+
+        kept, g = [], None
+        for i in range(N):
+            if keep:
+                kept.append(logit_buf.float())
+            if i == N - 1:
+                sample()
+            elif not graph or i == 0:                   # eager, and the warm-up step of graph=True
+                unit()
+            else:
+                if g is None:
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        unit()
+                g.replay()
+        return torch.stack(kept, 1) if keep else None
 
     def _generate_reference(self, idx, pl_dev, Tmax):
         """CPU (any device, plain PyTorch, fp32): the same prefill + cached steps with per-layer k, v lists"""

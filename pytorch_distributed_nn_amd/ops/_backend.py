@@ -157,6 +157,7 @@ _SIGS = {
     "pdnn_dropout_mask_attn": [P, I, I, I, F, P, I, P],
     "pdnn_embedding_fwd": [P, P, P, P, I, I, I, P],
     "pdnn_embedding_decode": [P, P, P, P, P, I, I, I, I, P],
+    "pdnn_sample_logits": [P, I, L, I, I, F, I, F, P, P, P, P, L, L, P, L, P, P, P],
     "pdnn_embedding_bwd": [P, P, P, P, I, I, I, P],
     "pdnn_embedding_bwd_scaled": [P, P, P, P, I, I, I, F, P],
     "pdnn_gemm_fp8": [P, L, P, L, P, L, I, I, I, P, P, I, P, P, P, I, P],

@@ -1727,6 +1727,54 @@ def embedding_decode(tok, lens, wte, wpe, out=None):
     return out
 
 
+def sample_logits(logits, tok, state, *, temperature=1.0, top_k=None, top_p=None, u=None, history=None, col0=0,
+                  finished=None, eos_token=None, thr=None, nkeep=None):
+    """One token per row of ``logits`` (bf16 or fp32 [B][V], rows may be a strided view, 1 <= V <= 65536) into ``tok``
+    int64 [B], one launch on the current stream: temperature, top-k, top-p, the eos mask and the draw as defined in the
+    header of csrc/kernels/sample.hip (ops.sampling.sample_reference is the same in torch).  ``state`` int64 [2] on the
+    device is (seed, step); row b draws u from (seed, step, b) unless ``u`` fp32 [B] overrides it.  ``history`` int64
+    [B][L] receives the token at column col0 + step.  With ``eos_token``, ``finished`` uint8 [B] is read and updated.
+    ``thr`` fp32 [B] and ``nkeep`` int32 [B] (optional) receive the final threshold and the size of the final set."""
+    _chk(torch.is_tensor(logits) and logits.is_cuda and logits.dtype in (BF16, F32) and logits.dim() == 2,
+         "sample_logits: logits must be a CUDA bf16 or fp32 [B][V] tensor")
+    B, V = logits.shape
+    _chk(B >= 1 and 1 <= V <= 65536, f"sample_logits: B >= 1 and 1 <= V <= 65536, got {tuple(logits.shape)}")
+    _chk(logits.stride(1) == 1 or V == 1, "sample_logits: logits must be contiguous along V")
+    ld = logits.stride(0) if B > 1 else V
+    _chk(ld >= V, f"sample_logits: row stride {ld} < V = {V}")
+    dev = logits.device
+
+    def vec(t, name, dtype, n=B):
+        _chk(torch.is_tensor(t) and t.dtype == dtype and t.shape == (n,) and t.is_contiguous() and t.device == dev,
+             f"sample_logits: {name} must be contiguous {dtype} [{n}] on the logits' device")
+    vec(tok, "tok", torch.int64)
+    vec(state, "state", torch.int64, 2)
+    temperature = float(temperature)
+    _chk(temperature >= 0.0, f"sample_logits: temperature must be >= 0, got {temperature!r}")     # NaN fails too
+    _chk(top_k is None or int(top_k) >= 1, f"sample_logits: top_k must be >= 1, got {top_k!r}")
+    _chk(top_p is None or float(top_p) > 0.0, f"sample_logits: top_p must be > 0, got {top_p!r}")
+    if u is not None:
+        vec(u, "u", F32)
+    if history is not None:
+        _chk(torch.is_tensor(history) and history.dtype == torch.int64 and history.dim() == 2 and history.shape[0] == B
+             and history.is_contiguous() and history.device == dev and 0 <= int(col0) < history.shape[1],
+             f"sample_logits: history must be contiguous int64 [{B}][L] on the logits' device with 0 <= col0 < L")
+    _chk((eos_token is None) or (finished is not None and 0 <= int(eos_token) < 2 ** 62),
+         "sample_logits: eos_token needs finished, and must be >= 0")
+    if finished is not None:
+        vec(finished, "finished", torch.uint8)
+    if thr is not None:
+        vec(thr, "thr", F32)
+    if nkeep is not None:
+        vec(nkeep, "nkeep", torch.int32)
+    k = 0 if top_k is None or int(top_k) >= V else int(top_k)
+    p = 0.0 if top_p is None or float(top_p) >= 1.0 else float(top_p)
+    call("pdnn_sample_logits", ptr(logits), 0 if logits.dtype == BF16 else 1, ld, B, V, temperature, k, p, ptr(state),
+         ptr(u), ptr(tok), ptr(history), history.shape[1] if history is not None else 0, int(col0), ptr(finished),
+         -1 if eos_token is None else int(eos_token), ptr(thr), ptr(nkeep), stream())
+    return tok
+
+
 def embedding_bwd(idx, g, dwte, dwpe, T, scale=1.0):
     """dwte[idx[r]] += scale * g[r], dwpe[r % T] += g[r] (fp32 atomics); either table may be None."""
     R, D = g.shape

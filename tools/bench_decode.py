@@ -17,9 +17,18 @@ With --skinny (the record behind ops.kernels.SKINNY_MAX_M, profiles/gemm_skinny.
   3. the model section at tuning decode_skinny = 1 and = 0 (0 is the path before the kernel, bit for bit: a same-process
      A/B), and the linears' share of the eager step at both.
 
+With --sample (profiles/sample_decode.txt) instead:
+
+  (a) one call of GPT2._sample (eager torch: topk, masked_fill, sort, softmax, multinomial) against one launch of
+      sample_logits at V = 50 304, B in {1, 8}, (k, p) in {(None, None), (50, None), (None, 0.9), (50, 0.9)}, both logits
+      dtypes (the torch sampler needs fp32: its bf16 figure includes the fp32 copy generate() makes); median us per call;
+  (b) ms per token of GPT-2 small, prompt 128, top_k = 50, top_p = 0.9: sampler="torch" eager and graph=True,
+      sampler="device" graph=True, and the greedy graph=True figure (the path of the parent commit) as the floor.
+
 One process, warm-up first, many iterations, medians of per-iteration event timings.  Nothing here is a pass/fail gate.
     python tools/bench_decode.py [--out profiles/attention_decode.txt] [--iters 200] [--tokens 64]
-    python tools/bench_decode.py --skinny [--out profiles/gemm_skinny.txt]"""
+    python tools/bench_decode.py --skinny [--out profiles/gemm_skinny.txt]
+    python tools/bench_decode.py --sample [--out profiles/sample_decode.txt]"""
 import argparse
 import os
 import statistics
@@ -174,6 +183,45 @@ def bench_model_ab(lines, tokens):
     lines.append("")
 
 
+def bench_sample(lines, iters, tokens, skip_model):
+    from pytorch_distributed_nn_amd.models.gpt2 import GPT2, build_gpt2
+    from pytorch_distributed_nn_amd.ops import kernels as K
+    V = 50304
+    lines.append(f"(a) one sampling call at V = {V}, temperature 0.8: GPT2._sample (eager torch) against sample_logits (one launch);")
+    lines.append(f"    median us per call of {iters} event-timed calls, 20 warm-up; torch on bf16 logits includes its fp32 copy")
+    lines.append("   B   top_k   top_p   dtype   torch us   device us   torch / device")
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    for B in (1, 8):
+        x32 = torch.randn(B, V, device="cuda") * 3
+        tok = torch.zeros(B, dtype=torch.int64, device="cuda")
+        state = torch.tensor([1, 0], dtype=torch.int64, device="cuda")
+        for k, p in ((None, None), (50, None), (None, 0.9), (50, 0.9)):
+            for dt in (torch.bfloat16, torch.float32):
+                x = x32.to(dt)
+                t = timed(lambda: GPT2._sample(x.float() if dt != torch.float32 else x, 0.8, k, gen, p), iters, 20) * 1e3
+                d = timed(lambda: K.sample_logits(x, tok, state, temperature=0.8, top_k=k, top_p=p), iters, 20) * 1e3
+                lines.append(f"  {B:2d}   {str(k):>5s}   {str(p):>5s}   {'bf16' if dt == torch.bfloat16 else 'fp32'}   {t:8.1f}   "
+                             f"{d:9.1f}   {t / d:14.2f}")
+    lines.append("")
+    if skip_model:
+        return
+    torch.manual_seed(0)
+    m = build_gpt2("gpt2_small").cuda().eval()
+    P = 128
+    lines.append(f"(b) GPT-2 small, prompt {P}, {tokens} new tokens, temperature 0.8, top_k = 50, top_p = 0.9; ms per token = whole")
+    lines.append("    call / tokens (prefill included), median of 5 calls; greedy graph is the path of the parent commit")
+    lines.append("   B   torch eager   torch graph   device graph   greedy graph (floor)")
+    for B in (1, 8):
+        idx = torch.randint(0, 50257, (B, P), device="cuda")
+        kw = dict(temperature=0.8, top_k=50, top_p=0.9)
+        te = timed(lambda: m.generate(idx, tokens, generator=gen, **kw), 5, 1) / tokens
+        tg = timed(lambda: m.generate(idx, tokens, generator=gen, graph=True, **kw), 5, 1) / tokens
+        dg = timed(lambda: m.generate(idx, tokens, sampler="device", seed=1, graph=True, **kw), 5, 1) / tokens
+        gg = timed(lambda: m.generate(idx, tokens, temperature=0.0, graph=True), 5, 1) / tokens
+        lines.append(f"  {B:2d}   {te:11.3f}   {tg:11.3f}   {dg:12.3f}   {gg:12.3f}")
+    lines.append("")
+
+
 def bench_model(lines, tokens):
     from pytorch_distributed_nn_amd.models.gpt2 import build_gpt2
     from pytorch_distributed_nn_amd.ops import linear as BL
@@ -232,10 +280,14 @@ def main():
     ap.add_argument("--tokens", type=int, default=64)
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--skinny", action="store_true", help="the gemm_skinny sections (profiles/gemm_skinny.txt)")
+    ap.add_argument("--sample", action="store_true", help="the sampling sections (profiles/sample_decode.txt)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_decode needs a GPU"
-    lines = [f"tools/bench_decode.py{' --skinny' if a.skinny else ''} on {torch.cuda.get_device_name(0)}", ""]
-    if a.skinny:
+    lines = [f"tools/bench_decode.py{' --skinny' if a.skinny else ' --sample' if a.sample else ''} on "
+             f"{torch.cuda.get_device_name(0)}", ""]
+    if a.sample:
+        bench_sample(lines, a.iters, a.tokens, a.skip_model)
+    elif a.skinny:
         bench_skinny(lines, min(a.iters, 30))
         if not a.skip_model:
             bench_model_ab(lines, a.tokens)

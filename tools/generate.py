@@ -44,6 +44,9 @@ def build_parser():
     ap.add_argument("--max-new-tokens", type=int, default=32)
     ap.add_argument("--temperature", type=float, default=1.0, help="0 = greedy")
     ap.add_argument("--top-k", type=int, default=None)
+    ap.add_argument("--top-p", type=float, default=None, help="nucleus sampling: keep the most probable tokens up to this mass")
+    ap.add_argument("--sampler", choices=["torch", "device"], default="torch",
+                    help="device: the sampling kernel and its counter-based generator, seeded by --seed")
     ap.add_argument("--eos-token", type=int, default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
@@ -71,10 +74,13 @@ def main(argv=None):
         raise SystemExit(f"--prompt-ids: token ids must be in [0, {V}), got {int(idx.min())}..{int(idx.max())}")
     dev = torch.device(args.device)
     model = model.to(dev).eval()
-    gen = torch.Generator(device=dev).manual_seed(args.seed)
+    if args.sampler == "device":
+        draw = dict(sampler="device", seed=args.seed)
+    else:
+        draw = dict(generator=torch.Generator(device=dev).manual_seed(args.seed))
     try:
         out = model.generate(idx.to(dev), args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
-                             eos_token=args.eos_token, generator=gen, graph=args.graph and dev.type == "cuda")
+                             top_p=args.top_p, eos_token=args.eos_token, graph=args.graph and dev.type == "cuda", **draw)
     except ValueError as e:
         raise SystemExit(str(e))
     for row in out.cpu().tolist():
