@@ -853,23 +853,6 @@ static void launch_fwd(const bf16_t* qkv, bf16_t* out, float* lse2, int B, int T
                        scale, mk);
 }
 
-// qkv [B*T][3*H*64] bf16 -> out [B*T][H*64] bf16, lse2 [B][H][T] fp32.  T % 128 == 0.
-PDNN_API int pdnn_flash_attn_fwd(const bf16_t* qkv, bf16_t* out, float* lse2, int B, int T, int H, float scale,
-                                 int causal, hipStream_t st) {
-    if (B < 1 || T < 1 || H < 1 || T % 128 || !qkv || !out || !lse2) return (int)hipErrorInvalidValue;
-    launch_fwd<false>(qkv, out, lse2, B, T, H, scale, causal, st);
-    PDNN_LAUNCH_RET;
-}
-
-// the same under the packed-document mask: doc_start, doc_end int32 [B][T] (pdnn_doc_bounds)
-PDNN_API int pdnn_flash_attn_doc_fwd(const bf16_t* qkv, bf16_t* out, float* lse2, int B, int T, int H, float scale,
-                                     const int* doc_start, const int* doc_end, hipStream_t st) {
-    if (B < 1 || T < 1 || H < 1 || T % 128 || !qkv || !out || !lse2 || !doc_start || !doc_end)
-        return (int)hipErrorInvalidValue;
-    launch_fwd<true>(qkv, out, lse2, B, T, H, scale, DocArg{doc_start, doc_end}, st);
-    PDNN_LAUNCH_RET;
-}
-
 // DOC at NF = 2 needs no scratch either (profiles/attention_doc_mask.txt), so attn_bwd_wide routes it like the plain
 // one.  DROP always takes NF = 1: at NF = 2 the sixteen words per fragment pair bring dK / dV to 254 - 256 VGPRs (no
 // scratch, but one wave / SIMD) and it measured slower than NF = 1 (profiles/attention_dropout.txt), so the NF = 2 DROP
@@ -916,62 +899,65 @@ static void launch_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dO, c
     launch_dq<false, DOC, DROP>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, mk, st);
 }
 
-// dO [B*T][H*64], out/lse2 from the forward -> dqkv [B*T][3*H*64]; delta: fp32 [B][H][T] scratch.
-PDNN_API int pdnn_flash_attn_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dO, const float* lse2,
-                                 float* delta, bf16_t* dqkv, int B, int T, int H, float scale, int causal,
-                                 hipStream_t st) {
-    if (B < 1 || T < 1 || H < 1 || T % 128 || !qkv || !out || !dO || !lse2 || !delta || !dqkv)
-        return (int)hipErrorInvalidValue;
-    launch_bwd<false>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, causal, st);
-    PDNN_LAUNCH_RET;
-}
+// The two entries.  One forward and one backward serve every variant; the optional arguments pick the kernels:
+//   doc_start, doc_end  int32 [B][T] (pdnn_doc_bounds), both null (plain) or both given (packed documents, DOC)
+//   p, state, site      dropout p on the probabilities (dropout_rng.h, DROP): p in [0, 1), quantised to thr / 256; state =
+//                       device int64[2] (seed, step), read by the kernels; site >= 0; T <= 65536 keeps the granule index
+//                       inside 32 bits.  p == 0 takes the kernels without DROP (they are faster): state may then be null
+//                       and site is ignored.
+// DOC and DROP exist under the causal mask only, so either with causal == 0 is refused; the plain kernels take ``causal``
+// as it comes.  The backward takes what the forward took.  Anything refused returns hipErrorInvalidValue, nothing launched.
+static bool attn_dims_ok(int B, int T, int H, bool ptrs) { return B >= 1 && T >= 1 && H >= 1 && T % 128 == 0 && ptrs; }
 
-PDNN_API int pdnn_flash_attn_doc_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dO, const float* lse2,
-                                     float* delta, bf16_t* dqkv, int B, int T, int H, float scale, const int* doc_start,
-                                     const int* doc_end, hipStream_t st) {
-    if (B < 1 || T < 1 || H < 1 || T % 128 || !qkv || !out || !dO || !lse2 || !delta || !dqkv || !doc_start || !doc_end)
-        return (int)hipErrorInvalidValue;
-    launch_bwd<true>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, DocArg{doc_start, doc_end}, st);
-    PDNN_LAUNCH_RET;
-}
+template <typename M> constexpr bool is_doc = std::is_same<M, DocArg>::value || std::is_same<M, DocDrop>::value;
+template <typename M> constexpr bool is_drop = std::is_same<M, CausalDrop>::value || std::is_same<M, DocDrop>::value;
 
-// Causal attention with dropout p on the probabilities (dropout_rng.h): state = device int64[2] (seed, step), read by
-// the kernels; doc_start / doc_end both null (plain causal) or both given (packed documents).  p in [0, 1), quantised
-// to thr / 256; T <= 65536 keeps the granule index inside 32 bits.  The backward takes what the forward took.
-static bool drop_arg(float p, const long long* state, int site, int T, const int* doc_start, const int* doc_end,
-                     pdrop::Arg* a) {
+// calls f with the kernels' last argument (int causal, DocArg, CausalDrop or DocDrop); false, f not called, when refused
+template <typename F>
+static bool with_mask(int causal, const int* doc_start, const int* doc_end, float p, const long long* state, int site,
+                      int T, F&& f) {
+    if ((doc_start == nullptr) != (doc_end == nullptr) || ((doc_start || p != 0.f) && !causal)) return false;
+    if (p == 0.f) {
+        if (doc_start)
+            f(DocArg{doc_start, doc_end});
+        else
+            f(causal);
+        return true;
+    }
     uint32_t thr;
-    if (!pdrop::threshold(p, &thr) || !state || site < 0 || T > 65536 || (doc_start == nullptr) != (doc_end == nullptr))
-        return false;
-    *a = pdrop::Arg{state, (uint32_t)site, thr, pdrop::scale_of(thr)};
+    if (!pdrop::threshold(p, &thr) || !state || site < 0 || T > 65536) return false;
+    const pdrop::Arg a{state, (uint32_t)site, thr, pdrop::scale_of(thr)};
+    if (doc_start)
+        f(DocDrop{DocArg{doc_start, doc_end}, a});
+    else
+        f(CausalDrop{1, a});
     return true;
 }
 
-PDNN_API int pdnn_flash_attn_drop_fwd(const bf16_t* qkv, bf16_t* out, float* lse2, int B, int T, int H, float scale,
-                                      float p, const long long* state, int site, const int* doc_start,
-                                      const int* doc_end, hipStream_t st) {
-    pdrop::Arg a;
-    if (B < 1 || T < 1 || H < 1 || T % 128 || !qkv || !out || !lse2 || !drop_arg(p, state, site, T, doc_start, doc_end, &a))
+// qkv [B*T][3*H*64] bf16 -> out [B*T][H*64] bf16, lse2 [B][H][T] fp32.  T % 128 == 0.
+PDNN_API int pdnn_flash_attn_fwd(const bf16_t* qkv, bf16_t* out, float* lse2, int B, int T, int H, float scale,
+                                 int causal, const int* doc_start, const int* doc_end, float p, const long long* state,
+                                 int site, hipStream_t st) {
+    if (!attn_dims_ok(B, T, H, qkv && out && lse2) ||
+        !with_mask(causal, doc_start, doc_end, p, state, site, T, [&](auto mk) {
+            using M = decltype(mk);
+            launch_fwd<is_doc<M>, is_drop<M>>(qkv, out, lse2, B, T, H, scale, mk, st);
+        }))
         return (int)hipErrorInvalidValue;
-    if (doc_start)
-        launch_fwd<true, true>(qkv, out, lse2, B, T, H, scale, DocDrop{DocArg{doc_start, doc_end}, a}, st);
-    else
-        launch_fwd<false, true>(qkv, out, lse2, B, T, H, scale, CausalDrop{1, a}, st);
     PDNN_LAUNCH_RET;
 }
 
-PDNN_API int pdnn_flash_attn_drop_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dO, const float* lse2,
-                                      float* delta, bf16_t* dqkv, int B, int T, int H, float scale, float p,
-                                      const long long* state, int site, const int* doc_start, const int* doc_end,
-                                      hipStream_t st) {
-    pdrop::Arg a;
-    if (B < 1 || T < 1 || H < 1 || T % 128 || !qkv || !out || !dO || !lse2 || !delta || !dqkv ||
-        !drop_arg(p, state, site, T, doc_start, doc_end, &a))
+// dO [B*T][H*64], out/lse2 from the forward -> dqkv [B*T][3*H*64]; delta: fp32 [B][H][T] scratch.
+PDNN_API int pdnn_flash_attn_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* dO, const float* lse2,
+                                 float* delta, bf16_t* dqkv, int B, int T, int H, float scale, int causal,
+                                 const int* doc_start, const int* doc_end, float p, const long long* state, int site,
+                                 hipStream_t st) {
+    if (!attn_dims_ok(B, T, H, qkv && out && dO && lse2 && delta && dqkv) ||
+        !with_mask(causal, doc_start, doc_end, p, state, site, T, [&](auto mk) {
+            using M = decltype(mk);
+            launch_bwd<is_doc<M>, is_drop<M>>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, mk, st);
+        }))
         return (int)hipErrorInvalidValue;
-    if (doc_start)
-        launch_bwd<true, true>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, DocDrop{DocArg{doc_start, doc_end}, a}, st);
-    else
-        launch_bwd<false, true>(qkv, out, dO, lse2, delta, dqkv, B, T, H, scale, CausalDrop{1, a}, st);
     PDNN_LAUNCH_RET;
 }
 

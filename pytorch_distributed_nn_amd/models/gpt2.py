@@ -281,10 +281,8 @@ class GPT2(nn.Module):
         for layer, blk in enumerate(tr.h):
             params, shadows = blk.fused_params()
             metas = blk.fp8_metas(x.device) if c.fp8 else None
-            conf = (B, T, c.n_head, c.eps, metas, doc)
-            if rates is not None and (rates[1] or rates[2]):
-                conf += ((rates[1], rates[2], snap, layer),)
-            x = TX.GPT2BlockFn.apply(x, conf, shadows, *params)
+            drop = (rates[1], rates[2], snap, layer) if rates is not None and (rates[1] or rates[2]) else None
+            x = TX.GPT2BlockFn.apply(x, TX.BlockConf(B, T, c.n_head, c.eps, metas, doc, drop), shadows, *params)
         if targets is None:
             xf = TX.layer_norm(x, tr.ln_f.weight, tr.ln_f.bias, c.eps)
             return OF.linear(xf, wte).view(B, T, -1)

@@ -141,16 +141,12 @@ _SIGS = {
     "pdnn_layernorm_bwd": [P, P, P, P, P, P, P, P, I, I, I, P],
     "pdnn_attn_softmax_fwd": [P, L, P, L, P, I, I, F, I, P],
     "pdnn_attn_softmax_bwd": [P, L, P, L, P, L, I, I, F, I, P],
-    "pdnn_flash_attn_fwd": [P, P, P, I, I, I, F, I, P],
-    "pdnn_flash_attn_bwd": [P, P, P, P, P, P, I, I, I, F, I, P],
-    "pdnn_flash_attn_doc_fwd": [P, P, P, I, I, I, F, P, P, P],
-    "pdnn_flash_attn_doc_bwd": [P, P, P, P, P, P, I, I, I, F, P, P, P],
+    "pdnn_flash_attn_fwd": [P, P, P, I, I, I, F, I, P, P, F, P, I, P],
+    "pdnn_flash_attn_bwd": [P, P, P, P, P, P, I, I, I, F, I, P, P, F, P, I, P],
     "pdnn_doc_bounds": [P, ctypes.c_longlong, P, P, I, I, P],
     "pdnn_attn_decode": [P, P, P, P, P, P, I, I, I, I, F, P],
     "pdnn_attn_decode_ws": [I, I, I, I],
     "pdnn_kv_cache_fill": [P, P, P, I, I, I, I, P],
-    "pdnn_flash_attn_drop_fwd": [P, P, P, I, I, I, F, F, P, I, P, P, P],
-    "pdnn_flash_attn_drop_bwd": [P, P, P, P, P, P, I, I, I, F, F, P, I, P, P, P],
     "pdnn_dropout_add_fwd": [P, P, P, L, I, F, P, I, P],
     "pdnn_dropout_bwd": [P, P, L, I, F, P, I, P],
     "pdnn_dropout_mask_rows": [P, L, I, F, P, I, P],

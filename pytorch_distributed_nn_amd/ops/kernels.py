@@ -1440,34 +1440,6 @@ def attn_softmax_bwd(P, dP, dS, rows, T, scale, causal=False):
          stream())
 
 
-def flash_attn_fwd(qkv, B, T, H, scale, causal=True):
-    """Fused attention, head dim 64: qkv [B*T][3*H*64] -> (out [B*T][H*64], lse2 [B][H][T])."""
-    _bf16_c(qkv, "flash_attn.qkv")
-    _chk(B >= 1 and T >= 1 and H >= 1 and qkv.shape == (B * T, 3 * H * 64) and T % 128 == 0,
-         f"flash_attn: qkv {tuple(qkv.shape)} B={B} T={T} H={H}")
-    out = torch.empty(B * T, H * 64, device=qkv.device, dtype=BF16)
-    lse2 = torch.empty(B, H, T, device=qkv.device, dtype=F32)
-    call("pdnn_flash_attn_fwd", ptr(qkv), ptr(out), ptr(lse2), B, T, H, float(scale), int(causal), stream())
-    return out, lse2
-
-
-def flash_attn_bwd(qkv, out, dout, lse2, B, T, H, scale, causal=True):
-    _bf16_c(qkv, "flash_attn_bwd.qkv")
-    _chk(B >= 1 and T >= 1 and H >= 1 and qkv.shape == (B * T, 3 * H * 64) and T % 128 == 0,
-         f"flash_attn_bwd: qkv {tuple(qkv.shape)} B={B} T={T} H={H}")
-    dout = dout.contiguous()
-    _chk(out.dtype == BF16 and out.shape == (B * T, H * 64) and out.is_contiguous(),
-         "flash_attn_bwd: out must be contiguous bf16 [B*T][H*64]")
-    _chk(dout.dtype == BF16 and dout.shape == out.shape, "flash_attn_bwd: dout must be bf16 of out's shape")
-    _chk(lse2.dtype == F32 and lse2.shape == (B, H, T) and lse2.is_contiguous(),
-         "flash_attn_bwd: lse2 must be contiguous fp32 [B][H][T]")
-    dqkv = torch.empty_like(qkv)
-    delta = torch.empty(B, H, T, device=qkv.device, dtype=F32)
-    call("pdnn_flash_attn_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse2), ptr(delta), ptr(dqkv), B, T, H, float(scale),
-         int(causal), stream())
-    return dqkv
-
-
 def doc_bounds(idx, eot):
     """Packed-document bounds of token ids idx int64 [B][T] on the device, no host read-back: (doc_start, doc_end) int32
     [B][T], the first token of t's document and one past its last.  A document ends with (and includes) its ``eot``."""
@@ -1488,35 +1460,58 @@ def _doc_chk(name, doc_start, doc_end, B, T, dev):
              f"{name}: {what} must be contiguous int32 [B][T] on {dev}")
 
 
-def flash_attn_doc_fwd(qkv, doc_start, doc_end, B, T, H, scale):
-    """flash_attn_fwd under the causal packed-document mask: query q of sequence b sees key k iff
-    doc_start[b][q] <= k <= q (bounds as from :func:`doc_bounds`)."""
-    _bf16_c(qkv, "flash_attn_doc.qkv")
+def _flash_chk(name, qkv, B, T, H, causal, doc, drop):
+    """The checks flash_attn_fwd / _bwd share -> (doc_start, doc_end, p, state, site) as the C entries take them."""
+    _bf16_c(qkv, f"{name}.qkv")
     _chk(B >= 1 and T >= 1 and H >= 1 and qkv.shape == (B * T, 3 * H * 64) and T % 128 == 0,
-         f"flash_attn_doc: qkv {tuple(qkv.shape)} B={B} T={T} H={H}")
-    _doc_chk("flash_attn_doc", doc_start, doc_end, B, T, qkv.device)
+         f"{name}: qkv {tuple(qkv.shape)} B={B} T={T} H={H}")
+    _chk(causal or (doc is None and drop is None), f"{name}: doc and drop exist under the causal mask only")
+    ds = de = state = None
+    p, site = 0.0, 0
+    if doc is not None:
+        _chk(isinstance(doc, tuple) and len(doc) == 2, f"{name}: doc must be (doc_start, doc_end)")
+        ds, de = doc
+        _doc_chk(name, ds, de, B, T, qkv.device)
+    if drop is not None:
+        _chk(isinstance(drop, tuple) and len(drop) == 3, f"{name}: drop must be (p, state, site)")
+        p, state, site = drop
+        p = _drop_chk(name, p, state, site, qkv.device)
+        _chk(p == 0.0 or T <= 65536, f"{name}: dropout needs T <= 65536, got T={T}")
+    return ptr(ds), ptr(de), p, ptr(state), site
+
+
+def _flash_bwd_chk(name, out, dout, lse2, B, T, H):
+    """The forward's results and the incoming gradient of flash_attn_bwd -> dout, contiguous."""
+    dout = dout.contiguous()
+    _chk(out.dtype == BF16 and out.shape == (B * T, H * 64) and out.is_contiguous(),
+         f"{name}: out must be contiguous bf16 [B*T][H*64]")
+    _chk(dout.dtype == BF16 and dout.shape == out.shape, f"{name}: dout must be bf16 of out's shape")
+    _chk(lse2.dtype == F32 and lse2.shape == (B, H, T) and lse2.is_contiguous(),
+         f"{name}: lse2 must be contiguous fp32 [B][H][T]")
+    return dout
+
+
+def flash_attn_fwd(qkv, B, T, H, scale, causal=True, *, doc=None, drop=None):
+    """Fused attention, head dim 64: qkv [B*T][3*H*64] -> (out [B*T][H*64], lse2 [B][H][T]).
+    ``doc`` = (doc_start, doc_end), bounds as from :func:`doc_bounds`: the causal packed-document mask, query q of
+    sequence b sees key k iff doc_start[b][q] <= k <= q.
+    ``drop`` = (p, state, site): dropout ``p`` on the probabilities, O = (P o keep) V / (1 - p_eff); lse2 is that of the
+    undropped softmax.  p == 0 runs the kernels without dropout.  Both need ``causal``."""
+    masks = _flash_chk("flash_attn", qkv, B, T, H, causal, doc, drop)
     out = torch.empty(B * T, H * 64, device=qkv.device, dtype=BF16)
     lse2 = torch.empty(B, H, T, device=qkv.device, dtype=F32)
-    call("pdnn_flash_attn_doc_fwd", ptr(qkv), ptr(out), ptr(lse2), B, T, H, float(scale), ptr(doc_start), ptr(doc_end),
-         stream())
+    call("pdnn_flash_attn_fwd", ptr(qkv), ptr(out), ptr(lse2), B, T, H, float(scale), int(causal), *masks, stream())
     return out, lse2
 
 
-def flash_attn_doc_bwd(qkv, out, dout, lse2, doc_start, doc_end, B, T, H, scale):
-    _bf16_c(qkv, "flash_attn_doc_bwd.qkv")
-    _chk(B >= 1 and T >= 1 and H >= 1 and qkv.shape == (B * T, 3 * H * 64) and T % 128 == 0,
-         f"flash_attn_doc_bwd: qkv {tuple(qkv.shape)} B={B} T={T} H={H}")
-    dout = dout.contiguous()
-    _chk(out.dtype == BF16 and out.shape == (B * T, H * 64) and out.is_contiguous(),
-         "flash_attn_doc_bwd: out must be contiguous bf16 [B*T][H*64]")
-    _chk(dout.dtype == BF16 and dout.shape == out.shape, "flash_attn_doc_bwd: dout must be bf16 of out's shape")
-    _chk(lse2.dtype == F32 and lse2.shape == (B, H, T) and lse2.is_contiguous(),
-         "flash_attn_doc_bwd: lse2 must be contiguous fp32 [B][H][T]")
-    _doc_chk("flash_attn_doc_bwd", doc_start, doc_end, B, T, qkv.device)
+def flash_attn_bwd(qkv, out, dout, lse2, B, T, H, scale, causal=True, *, doc=None, drop=None):
+    """dqkv of :func:`flash_attn_fwd` from its results and ``dout``; causal, doc and drop as the forward had them."""
+    masks = _flash_chk("flash_attn_bwd", qkv, B, T, H, causal, doc, drop)
+    dout = _flash_bwd_chk("flash_attn_bwd", out, dout, lse2, B, T, H)
     dqkv = torch.empty_like(qkv)
     delta = torch.empty(B, H, T, device=qkv.device, dtype=F32)
-    call("pdnn_flash_attn_doc_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse2), ptr(delta), ptr(dqkv), B, T, H,
-         float(scale), ptr(doc_start), ptr(doc_end), stream())
+    call("pdnn_flash_attn_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse2), ptr(delta), ptr(dqkv), B, T, H, float(scale),
+         int(causal), *masks, stream())
     return dqkv
 
 
@@ -1649,50 +1644,6 @@ def dropout_mask_attn(B, H, T, p, state, site):
     out = torch.empty(B, H, T, T, device=state.device, dtype=torch.uint8)
     call("pdnn_dropout_mask_attn", ptr(out), B, H, T, p, ptr(state), site, stream())
     return out
-
-
-def flash_attn_drop_fwd(qkv, B, T, H, scale, p, state, site, doc_start=None, doc_end=None):
-    """flash_attn_fwd (or flash_attn_doc_fwd, with bounds) with dropout ``p`` on the probabilities: O = (P o keep) V /
-    (1 - p_eff); lse2 is that of the undropped softmax.  p == 0 runs the plain / DOC entry."""
-    _bf16_c(qkv, "flash_attn_drop.qkv")
-    _chk(B >= 1 and T >= 1 and H >= 1 and qkv.shape == (B * T, 3 * H * 64) and T % 128 == 0 and T <= 65536,
-         f"flash_attn_drop: qkv {tuple(qkv.shape)} B={B} T={T} H={H}")
-    p = _drop_chk("flash_attn_drop", p, state, site, qkv.device)
-    _chk((doc_start is None) == (doc_end is None), "flash_attn_drop: doc_start and doc_end go together")
-    if doc_start is not None:
-        _doc_chk("flash_attn_drop", doc_start, doc_end, B, T, qkv.device)
-    if p == 0.0:
-        return (flash_attn_fwd(qkv, B, T, H, scale) if doc_start is None
-                else flash_attn_doc_fwd(qkv, doc_start, doc_end, B, T, H, scale))
-    out = torch.empty(B * T, H * 64, device=qkv.device, dtype=BF16)
-    lse2 = torch.empty(B, H, T, device=qkv.device, dtype=F32)
-    call("pdnn_flash_attn_drop_fwd", ptr(qkv), ptr(out), ptr(lse2), B, T, H, float(scale), p, ptr(state), site,
-         ptr(doc_start), ptr(doc_end), stream())
-    return out, lse2
-
-
-def flash_attn_drop_bwd(qkv, out, dout, lse2, B, T, H, scale, p, state, site, doc_start=None, doc_end=None):
-    _bf16_c(qkv, "flash_attn_drop_bwd.qkv")
-    _chk(B >= 1 and T >= 1 and H >= 1 and qkv.shape == (B * T, 3 * H * 64) and T % 128 == 0 and T <= 65536,
-         f"flash_attn_drop_bwd: qkv {tuple(qkv.shape)} B={B} T={T} H={H}")
-    p = _drop_chk("flash_attn_drop_bwd", p, state, site, qkv.device)
-    _chk((doc_start is None) == (doc_end is None), "flash_attn_drop_bwd: doc_start and doc_end go together")
-    if doc_start is not None:
-        _doc_chk("flash_attn_drop_bwd", doc_start, doc_end, B, T, qkv.device)
-    if p == 0.0:
-        return (flash_attn_bwd(qkv, out, dout, lse2, B, T, H, scale) if doc_start is None
-                else flash_attn_doc_bwd(qkv, out, dout, lse2, doc_start, doc_end, B, T, H, scale))
-    dout = dout.contiguous()
-    _chk(out.dtype == BF16 and out.shape == (B * T, H * 64) and out.is_contiguous(),
-         "flash_attn_drop_bwd: out must be contiguous bf16 [B*T][H*64]")
-    _chk(dout.dtype == BF16 and dout.shape == out.shape, "flash_attn_drop_bwd: dout must be bf16 of out's shape")
-    _chk(lse2.dtype == F32 and lse2.shape == (B, H, T) and lse2.is_contiguous(),
-         "flash_attn_drop_bwd: lse2 must be contiguous fp32 [B][H][T]")
-    dqkv = torch.empty_like(qkv)
-    delta = torch.empty(B, H, T, device=qkv.device, dtype=F32)
-    call("pdnn_flash_attn_drop_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse2), ptr(delta), ptr(dqkv), B, T, H,
-         float(scale), p, ptr(state), site, ptr(doc_start), ptr(doc_end), stream())
-    return dqkv
 
 
 def embedding_fwd(idx, wte, wpe, T):

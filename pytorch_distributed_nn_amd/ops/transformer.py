@@ -26,6 +26,7 @@ skipping + row-softmax kernels).
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -388,17 +389,62 @@ class _Sink:
             grad_ready(p)
 
 
+class BlockConf(NamedTuple):
+    """What one block needs besides tensors and parameters; a plain tuple of the first four fields or more serves too
+    (``BlockConf(*t)``)."""
+    B: int
+    T: int
+    H: int
+    eps: float
+    metas: object = None        # the block's fp8 metas: the forward GEMMs run on the fp8 engine
+    doc: object = None          # (doc_start, doc_end) int32 [B][T]: packed-document mask
+    drop: object = None         # (attn_pdrop, resid_pdrop, state snapshot, layer) of a training forward with dropout
+
+
+_NO_DROP = (0.0, 0.0, None, 0)
+
+
+class _BlockAttn:
+    """The attention of one block on its packed qkv [B*T][3D]: the flash kernels where they apply (:func:`use_flash`),
+    else the materialised chain, which has neither a document mask nor dropout and refuses both."""
+
+    def __init__(self, conf, D):
+        self.B, self.T, self.H = B, T, H = conf[:3]
+        self.flash = use_flash(T, D, H)
+        self.scale = 1.0 / math.sqrt(D // H)
+        self.doc = conf.doc
+        p_attn, _, dstate, layer = conf.drop or _NO_DROP
+        # the probabilities never leave the kernel's registers: the mask is drawn inside it, at site 4 * layer
+        self.drop = (p_attn, dstate, 4 * layer) if p_attn > 0 else None
+        if self.doc is not None and not self.flash:
+            raise ValueError(f"packed-document attention needs the fused kernels (head dim 64, T % 128 == 0); got head "
+                             f"dim {D // H}, T = {T}: the unfused attention chain has no document mask")
+        if self.drop is not None and not self.flash:
+            raise ValueError(f"attention dropout needs the fused kernels (head dim 64, T % 128 == 0); got head dim "
+                             f"{D // H}, T = {T}: the unfused attention chain has no dropout (attn_pdrop = 0 runs it)")
+
+    def fwd(self, qkv):
+        """-> y, P, S: P is lse2 and S None on the flash kernels; the chain's S is the backward's fp32 dP scratch"""
+        if self.flash:
+            return (*K.flash_attn_fwd(qkv, self.B, self.T, self.H, self.scale, doc=self.doc, drop=self.drop), None)
+        return attention_fwd(qkv, self.B, self.T, self.H)
+
+    def bwd(self, qkv, y, dy, P, S):
+        if self.flash:
+            return K.flash_attn_bwd(qkv, y, dy, P, self.B, self.T, self.H, self.scale, doc=self.doc, drop=self.drop)
+        return attention_bwd(dy, qkv, P, self.B, self.T, self.H, dS_buf=S)
+
+
 class GPT2BlockFn(torch.autograd.Function):
     """params: ln1_w, ln1_b, attn_w, attn_b, proj_w, proj_b, ln2_w, ln2_b, fc_w, fc_b, fc2_w, fc2_b
-    shadows: bf16 copies of attn_w [3D][D], proj_w [D][D], fc_w [4D][D], fc2_w [D][4D]."""
+    shadows: bf16 copies of attn_w [3D][D], proj_w [D][D], fc_w [4D][D], fc2_w [D][4D].  conf: :class:`BlockConf`."""
 
     @staticmethod
     def forward(ctx, x, conf, shadows, *params):
-        B, T, H, eps = conf[:4]
-        metas = conf[4] if len(conf) > 4 else None
-        doc = conf[5] if len(conf) > 5 else None        # (doc_start, doc_end) int32 [B][T]: packed-document mask
-        # (attn_pdrop, resid_pdrop, state snapshot, layer) of a training forward with dropout, else None
-        p_attn, p_res, dstate, layer = (conf[6] if len(conf) > 6 and conf[6] is not None else (0.0, 0.0, None, 0))
+        conf = BlockConf(*conf)
+        eps, metas = conf.eps, conf.metas
+        _, p_res, dstate, layer = conf.drop or _NO_DROP
+        attn = _BlockAttn(conf, x.shape[1])
         ln1w, ln1b, _, attn_b, _, proj_b, ln2w, ln2b, _, fc_b, _, fc2_b = params
         wqkv, wproj, wfc, wfc2 = shadows
         if metas is not None:
@@ -411,26 +457,7 @@ class GPT2BlockFn(torch.autograd.Function):
                 return BL.linear_fwd(inp, wk, **kw)
         ln1, m1, r1 = K.layernorm_fwd(x, ln1w, ln1b, eps)
         qkv = lin(ln1, 2, wqkv, bias=attn_b)
-        D = x.shape[1]
-        flash = use_flash(T, D, H)
-        if doc is not None and not flash:
-            raise ValueError(f"packed-document attention needs the fused kernels (head dim 64, T % 128 == 0); got head "
-                             f"dim {D // H}, T = {T}: the unfused attention chain has no document mask")
-        if p_attn > 0 and not flash:
-            raise ValueError(f"attention dropout needs the fused kernels (head dim 64, T % 128 == 0); got head dim "
-                             f"{D // H}, T = {T}: the unfused attention chain has no dropout (attn_pdrop = 0 runs it)")
-        if p_attn > 0:      # the probabilities never leave the kernel's registers: the mask is drawn inside it
-            y, P = K.flash_attn_drop_fwd(qkv, B, T, H, 1.0 / math.sqrt(D // H), p_attn, dstate, 4 * layer,
-                                         *(doc if doc is not None else (None, None)))
-            S = None
-        elif doc is not None:
-            y, P = K.flash_attn_doc_fwd(qkv, doc[0], doc[1], B, T, H, 1.0 / math.sqrt(D // H))
-            S = None
-        elif flash:
-            y, P = K.flash_attn_fwd(qkv, B, T, H, 1.0 / math.sqrt(D // H))     # P := lse2
-            S = None
-        else:
-            y, P, S = attention_fwd(qkv, B, T, H)
+        y, P, S = attn.fwd(qkv)
         if p_res > 0:       # the branch output is dropped before the add: GEMM with bias only, then one row pass
             x1 = lin(y, 4, wproj, bias=proj_b)
             K.dropout_add_fwd(x1, x, p_res, dstate, 4 * layer + 1, out=x1)
@@ -446,7 +473,7 @@ class GPT2BlockFn(torch.autograd.Function):
             x2 = lin(h, 10, wfc2, bias=fc2_b, res=x1)
         ctx.save_for_backward(x, ln1, m1, r1, qkv, P, y, x1, ln2, m2, r2, u, h, ln1w, ln2w, *shadows)
         ctx.conf = conf
-        ctx.flash = flash
+        ctx.attn = attn
         ctx.S = S          # materialised path: reused as the fp32 dP scratch in backward
         ctx.params = params
         return x2
@@ -454,7 +481,6 @@ class GPT2BlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (x, ln1, m1, r1, qkv, P, y, x1, ln2, m2, r2, u, h, ln1w, ln2w, wqkv, wproj, wfc, wfc2) = ctx.saved_tensors
-        B, T, H, eps = ctx.conf[:4]
         Pm = ctx.params
         ctx.params = None
         sink = _Sink()
@@ -463,8 +489,7 @@ class GPT2BlockFn(torch.autograd.Function):
             # the four data-gradient GEMMs' transposed weights of this block in one launch, just before use
             from .functional import prefetch_weight_t
             prefetch_weight_t((Pm[10], Pm[8], Pm[4], Pm[2]))
-        p_attn, p_res, dstate, layer = (ctx.conf[6] if len(ctx.conf) > 6 and ctx.conf[6] is not None
-                                        else (0.0, 0.0, None, 0))
+        _, p_res, dstate, layer = ctx.conf.drop or _NO_DROP
         # MLP (resid_pdrop: the branch sees the masked gradient, the residual path -- LN2's dres -- the whole one)
         gm = K.dropout_bwd(g, p_res, dstate, 4 * layer + 2) if p_res > 0 else g
         du = BL.linear_dgrad(gm, wfc2, dgelu=u, p=Pm[10])                      # (g . Wfc2) * gelu'(u)
@@ -476,16 +501,7 @@ class GPT2BlockFn(torch.autograd.Function):
         dm = K.dropout_bwd(dx1, p_res, dstate, 4 * layer + 1) if p_res > 0 else dx1
         dy = BL.linear_dgrad(dm, wproj, p=Pm[4])
         dproj_w, dproj_b = sink.linear(Pm[4], Pm[5], dm, y)
-        doc = ctx.conf[5] if len(ctx.conf) > 5 else None
-        if p_attn > 0:
-            dqkv = K.flash_attn_drop_bwd(qkv, y, dy, P, B, T, H, 1.0 / math.sqrt(x.shape[1] // H), p_attn, dstate,
-                                         4 * layer, *(doc if doc is not None else (None, None)))
-        elif doc is not None:
-            dqkv = K.flash_attn_doc_bwd(qkv, y, dy, P, doc[0], doc[1], B, T, H, 1.0 / math.sqrt(x.shape[1] // H))
-        elif ctx.flash:
-            dqkv = K.flash_attn_bwd(qkv, y, dy, P, B, T, H, 1.0 / math.sqrt(x.shape[1] // H))
-        else:
-            dqkv = attention_bwd(dy, qkv, P, B, T, H, dS_buf=ctx.S)
+        dqkv = ctx.attn.bwd(qkv, y, dy, P, ctx.S)
         ctx.S = None
         dln1 = BL.linear_dgrad(dqkv, wqkv, p=Pm[2])
         dattn_w, dattn_b = sink.linear(Pm[2], Pm[3], dqkv, ln1)
@@ -525,18 +541,20 @@ class KVCache:
 
 def block_prefill(x, conf, shadows, params, cache, layer):
     """One block over the whole (padded) prompt, the forward kernel sequence of :class:`GPT2BlockFn` with nothing saved:
-    x bf16 [B*T][D], conf = (B, T, H, eps) with T % 128 == 0 -> x2; the K and V of every position also go into slots
-    0..T-1 of ``cache`` layer ``layer``.  The linears are bf16 (BL.linear_fwd) whatever config.fp8 says."""
+    x bf16 [B*T][D], conf = (B, T, H, eps) or a :class:`BlockConf`, T % 128 == 0 -> x2; the K and V of every position
+    also go into slots 0..T-1 of ``cache`` layer ``layer``.  The linears are bf16 (BL.linear_fwd) whatever config.fp8
+    says."""
     B, T, H, eps = conf[:4]
     ln1w, ln1b, _, attn_b, _, proj_b, ln2w, ln2b, _, fc_b, _, fc2_b = params
     wqkv, wproj, wfc, wfc2 = shadows
-    D = x.shape[1]
-    if not use_flash(T, D, H):
-        raise ValueError(f"generation needs the fused kernels (head dim 64, T % 128 == 0); got head dim {D // H}, T = {T}")
+    attn = _BlockAttn(BlockConf(B, T, H, eps), x.shape[1])          # a prompt is one document, and nothing is dropped
+    if not attn.flash:
+        raise ValueError(f"generation needs the fused kernels (head dim 64, T % 128 == 0); got head dim "
+                         f"{x.shape[1] // H}, T = {T}")
     ln1, _, _ = K.layernorm_fwd(x, ln1w, ln1b, eps)
     qkv = BL.linear_fwd(ln1, wqkv, bias=attn_b)
     K.kv_cache_fill(qkv, cache.k[layer], cache.v[layer], B, T)
-    y, _ = K.flash_attn_fwd(qkv, B, T, H, 1.0 / math.sqrt(D // H))
+    y, _, _ = attn.fwd(qkv)
     x1 = BL.linear_fwd(y, wproj, bias=proj_b, res=x)
     ln2, _, _ = K.layernorm_fwd(x1, ln2w, ln2b, eps)
     h = BL.linear_fwd(ln2, wfc, bias=fc_b, act=2)

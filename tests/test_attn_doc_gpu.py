@@ -1,4 +1,4 @@
-"""The packed-document flash kernels (csrc/kernels/attention.hip, DOC variants; ops.kernels.flash_attn_doc_fwd / _bwd,
+"""The packed-document flash kernels (csrc/kernels/attention.hip, DOC variants; ops.kernels.flash_attn_fwd / _bwd with ``doc``,
 doc_bounds) against the float64 reference of tests/attn_doc_ref.py, element by element, over every element, with
 the bounds derived there: every layout x shape x family, the backward under all eight (attn_bwd_wide, attn_delta_in_dq)
 variants on attn_doc_ref.CROSS_SHAPES and under the defaults elsewhere, handed the float64 forward rounded to bf16 /
@@ -78,8 +78,8 @@ def test_doc_forward(K, shape):
     for layout in R.LAYOUTS:
         for family in R.FAMILIES:
             c = _case(family, layout, shape)
-            O, lse2 = K.flash_attn_doc_fwd(c.qkv, c.ds, c.de, B, T, H, SCALE)
-            O2, lse2b = K.flash_attn_doc_fwd(c.qkv, c.ds, c.de, B, T, H, SCALE)
+            O, lse2 = K.flash_attn_fwd(c.qkv, B, T, H, SCALE, doc=(c.ds, c.de))
+            O2, lse2b = K.flash_attn_fwd(c.qkv, B, T, H, SCALE, doc=(c.ds, c.de))
             assert A.bits_equal(O, O2) and A.bits_equal(lse2, lse2b), (layout, family, "not repeatable: a race")
             try:
                 r = R.check_doc_fwd(c.qkv, O, lse2, c.ds, c.de, B, T, H, SCALE, ref=c.fwd)
@@ -98,8 +98,8 @@ def test_doc_backward(K, shape, wide, delta_in_dq):
         for layout in R.LAYOUTS:
             for family in R.FAMILIES:
                 c = _case(family, layout, shape)
-                dqkv = K.flash_attn_doc_bwd(c.qkv, c.Og, c.dO, c.lg, c.ds, c.de, B, T, H, SCALE)
-                again = K.flash_attn_doc_bwd(c.qkv, c.Og, c.dO, c.lg, c.ds, c.de, B, T, H, SCALE)
+                dqkv = K.flash_attn_bwd(c.qkv, c.Og, c.dO, c.lg, B, T, H, SCALE, doc=(c.ds, c.de))
+                again = K.flash_attn_bwd(c.qkv, c.Og, c.dO, c.lg, B, T, H, SCALE, doc=(c.ds, c.de))
                 assert A.bits_equal(dqkv, again), (layout, family, "not repeatable: a race")
                 try:
                     r = R.check_doc_bwd(c.qkv, c.Og, c.dO, c.lg, dqkv, c.ds, c.de, B, T, H, SCALE, ref=c.bwd)
@@ -120,12 +120,12 @@ def test_single_document_is_the_plain_causal_kernel_bitwise(K, shape):
     for family in R.FAMILIES:
         qkv, dO = (t.cuda() for t in R.gen_doc(family, B, T, H, SCALE))
         O, lse2 = K.flash_attn_fwd(qkv, B, T, H, SCALE, True)
-        Od, lse2d = K.flash_attn_doc_fwd(qkv, ds, de, B, T, H, SCALE)
+        Od, lse2d = K.flash_attn_fwd(qkv, B, T, H, SCALE, doc=(ds, de))
         assert A.bits_equal(O, Od) and A.bits_equal(lse2, lse2d), family
         for wide, delta_in_dq in VARIANTS:
             with _variant(K, wide, delta_in_dq):
                 want = K.flash_attn_bwd(qkv, O, dO, lse2, B, T, H, SCALE, True)
-                got = K.flash_attn_doc_bwd(qkv, O, dO, lse2, ds, de, B, T, H, SCALE)
+                got = K.flash_attn_bwd(qkv, O, dO, lse2, B, T, H, SCALE, doc=(ds, de))
             assert A.bits_equal(want, got), (family, wide, delta_in_dq)
 
 
@@ -139,7 +139,7 @@ def test_documents_are_isolated_bitwise(K, layout):
     other, _ = (t.cuda() for t in R.gen_doc("next_key", B, T, H, SCALE))
     other = other.clone()
     other[::3] *= 2.0 ** 60
-    O, lse2 = K.flash_attn_doc_fwd(qkv, ds, de, B, T, H, SCALE)
+    O, lse2 = K.flash_attn_fwd(qkv, B, T, H, SCALE, doc=(ds, de))
     tok = torch.arange(T, device="cuda")
     for b in range(B):
         starts = R.layout_starts(R.LAYOUTS[(R.LAYOUTS.index(layout) + b) % len(R.LAYOUTS)], T)
@@ -149,13 +149,13 @@ def test_documents_are_isolated_bitwise(K, layout):
             keep[b] = (tok >= s) & (tok < e)
             kf = keep.reshape(B * T)
             mixed = torch.where(kf[:, None], qkv, other)
-            Om, lm = K.flash_attn_doc_fwd(mixed, ds, de, B, T, H, SCALE)
+            Om, lm = K.flash_attn_fwd(mixed, B, T, H, SCALE, doc=(ds, de))
             assert A.bits_equal(Om[kf], O[kf]), (layout, b, s, "O of the kept document changed")
             assert A.bits_equal(lm[b, :, s:e], lse2[b, :, s:e]), (layout, b, s, "lse2 of the kept document changed")
             dOz = torch.where(kf[:, None], dO, torch.zeros_like(dO))
             for wide, delta_in_dq in ((3, 1), (0, 0)):
                 with _variant(K, wide, delta_in_dq):
-                    dqkv = K.flash_attn_doc_bwd(qkv, O, dOz, lse2, ds, de, B, T, H, SCALE)
+                    dqkv = K.flash_attn_bwd(qkv, O, dOz, lse2, B, T, H, SCALE, doc=(ds, de))
                 assert bool((dqkv[~kf] == 0).all()), (layout, b, s, wide, "gradient leaked out of the document")
                 assert torch.isfinite(dqkv.float()).all()
 
@@ -165,7 +165,7 @@ def test_unit_layout(K):
     B, T, H = 3, 128, 2
     t = torch.arange(T, dtype=torch.int32).expand(B, T).contiguous().cuda()
     qkv, _ = (x.cuda() for x in R.gen_doc("gauss", B, T, H, SCALE))
-    O, lse2 = K.flash_attn_doc_fwd(qkv, t, t + 1, B, T, H, SCALE)
+    O, lse2 = K.flash_attn_fwd(qkv, B, T, H, SCALE, doc=(t, t + 1))
     q, k, v = (x.double() for x in A.split_heads(qkv, B, T, H))
     c = A.f32(SCALE) * A.LOG2E
     want = c * (q * k).sum(-1)
@@ -228,25 +228,25 @@ def test_wrappers_reject_bad_arguments(K, monkeypatch):
     no = pytest.raises(ValueError)
     for b, t, h in ((0, T, H), (B, 0, H), (B, T, 0), (-1, T, H), (B, 64, H)):
         with no:
-            K.flash_attn_doc_fwd(qkv, ds, de, b, t, h, SCALE)
+            K.flash_attn_fwd(qkv, b, t, h, SCALE, doc=(ds, de))
         with no:
-            K.flash_attn_doc_bwd(qkv, out, out, lse2, ds, de, b, t, h, SCALE)
+            K.flash_attn_bwd(qkv, out, out, lse2, b, t, h, SCALE, doc=(ds, de))
     bad = {"none": None, "int64": ds.long(), "strided": torch.zeros(B, 2 * T, device="cuda", dtype=torch.int32)[:, ::2],
            "shape": ds.reshape(T, B)[:T - 1], "flat": ds.reshape(-1), "cpu": ds.cpu()}
     for name, t in bad.items():
         for args in ((t, de), (ds, t)):
             with no:
-                K.flash_attn_doc_fwd(qkv, *args, B, T, H, SCALE)
+                K.flash_attn_fwd(qkv, B, T, H, SCALE, doc=args)
             with no:
-                K.flash_attn_doc_bwd(qkv, out, out, lse2, *args, B, T, H, SCALE)
+                K.flash_attn_bwd(qkv, out, out, lse2, B, T, H, SCALE, doc=args)
     with no:
-        K.flash_attn_doc_fwd(qkv.float(), ds, de, B, T, H, SCALE)
+        K.flash_attn_fwd(qkv.float(), B, T, H, SCALE, doc=(ds, de))
     with no:
-        K.flash_attn_doc_bwd(qkv, out.float(), out, lse2, ds, de, B, T, H, SCALE)
+        K.flash_attn_bwd(qkv, out.float(), out, lse2, B, T, H, SCALE, doc=(ds, de))
     with no:
-        K.flash_attn_doc_bwd(qkv, out, out, lse2.double(), ds, de, B, T, H, SCALE)
+        K.flash_attn_bwd(qkv, out, out, lse2.double(), B, T, H, SCALE, doc=(ds, de))
     with no:
-        K.flash_attn_doc_bwd(qkv, out, out.float(), lse2, ds, de, B, T, H, SCALE)
+        K.flash_attn_bwd(qkv, out, out.float(), lse2, B, T, H, SCALE, doc=(ds, de))
     for t in (idx.int(), idx.reshape(-1), idx.cpu(), torch.zeros(B, 2 * T, device="cuda", dtype=torch.int64)[:, ::2],
               torch.zeros(0, T, device="cuda", dtype=torch.int64)):
         with no:
@@ -255,7 +255,7 @@ def test_wrappers_reject_bad_arguments(K, monkeypatch):
         K.doc_bounds(idx, 5.0)
     monkeypatch.undo()
     K.doc_bounds(idx, 5)                                           # well-formed calls still go through
-    K.flash_attn_doc_bwd(qkv, out, out, lse2, ds, de, B, T, H, SCALE)
+    K.flash_attn_bwd(qkv, out, out, lse2, B, T, H, SCALE, doc=(ds, de))
     torch.cuda.synchronize()
 
 
@@ -269,22 +269,25 @@ def test_c_entry_points_refuse_before_launching(K):
     de = torch.full((B, T), T, device="cuda", dtype=torch.int32)
     idx = torch.zeros(B, T, device="cuda", dtype=torch.int64)
     p, st = K.ptr, K.stream()
+    nodrop = (0.0, None, 0)                                        # p, state, site
     no = pytest.raises(HipError)
     for b, t, h in ((0, T, H), (B, 0, H), (B, T, 0), (-1, T, H), (B, -128, H), (B, 64, H)):
         with no:
-            K.call("pdnn_flash_attn_doc_fwd", p(qkv), p(out), p(lse2), b, t, h, SCALE, p(ds), p(de), st)
+            K.call("pdnn_flash_attn_fwd", p(qkv), p(out), p(lse2), b, t, h, SCALE, 1, p(ds), p(de), *nodrop, st)
         with no:
-            K.call("pdnn_flash_attn_doc_bwd", p(qkv), p(out), p(out), p(lse2), p(lse2), p(qkv), b, t, h, SCALE, p(ds),
-                   p(de), st)
+            K.call("pdnn_flash_attn_bwd", p(qkv), p(out), p(out), p(lse2), p(lse2), p(qkv), b, t, h, SCALE, 1, p(ds),
+                   p(de), *nodrop, st)
     for a, b in ((None, p(de)), (p(ds), None)):
         with no:
-            K.call("pdnn_flash_attn_doc_fwd", p(qkv), p(out), p(lse2), B, T, H, SCALE, a, b, st)
+            K.call("pdnn_flash_attn_fwd", p(qkv), p(out), p(lse2), B, T, H, SCALE, 1, a, b, *nodrop, st)
         with no:
-            K.call("pdnn_flash_attn_doc_bwd", p(qkv), p(out), p(out), p(lse2), p(lse2), p(qkv), B, T, H, SCALE, a, b, st)
+            K.call("pdnn_flash_attn_bwd", p(qkv), p(out), p(out), p(lse2), p(lse2), p(qkv), B, T, H, SCALE, 1, a, b,
+                   *nodrop, st)
     with no:
-        K.call("pdnn_flash_attn_doc_fwd", p(qkv), p(out), None, B, T, H, SCALE, p(ds), p(de), st)
+        K.call("pdnn_flash_attn_fwd", p(qkv), p(out), None, B, T, H, SCALE, 1, p(ds), p(de), *nodrop, st)
     with no:
-        K.call("pdnn_flash_attn_doc_bwd", p(qkv), None, p(out), p(lse2), p(lse2), p(qkv), B, T, H, SCALE, p(ds), p(de), st)
+        K.call("pdnn_flash_attn_bwd", p(qkv), None, p(out), p(lse2), p(lse2), p(qkv), B, T, H, SCALE, 1, p(ds), p(de),
+               *nodrop, st)
     for b, t in ((0, T), (B, 0), (-1, T), (B, -1)):
         with no:
             K.call("pdnn_doc_bounds", p(idx), 5, p(ds), p(de), b, t, st)
@@ -309,8 +312,8 @@ def test_bounds_forward_backward_in_one_graph(K):
 
     def run(idx):
         ds, de = K.doc_bounds(idx, E)
-        O, lse2 = K.flash_attn_doc_fwd(qkv, ds, de, B, T, H, SCALE)
-        return O, lse2, K.flash_attn_doc_bwd(qkv, O, dO, lse2, ds, de, B, T, H, SCALE)
+        O, lse2 = K.flash_attn_fwd(qkv, B, T, H, SCALE, doc=(ds, de))
+        return O, lse2, K.flash_attn_bwd(qkv, O, dO, lse2, B, T, H, SCALE, doc=(ds, de))
 
     eager = [tuple(t.clone() for t in run(tok)) for tok in toks]
     assert not A.bits_equal(eager[0][0], eager[1][0])

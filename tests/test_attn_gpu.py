@@ -238,16 +238,17 @@ def test_c_entry_points_refuse_before_launching(K):
     v = torch.ones(4, device="cuda")
     slab = K.stat_bins(64, x.device)
     p, st = K.ptr, K.stream()
+    plain = (None, None, 0.0, None, 0)                             # doc_start, doc_end, p, state, site
     no = pytest.raises(HipError)
     for b, t, h in ((0, T, H), (B, 0, H), (B, T, 0), (-1, T, H), (B, -128, H), (B, 64, H)):
         with no:
-            K.call("pdnn_flash_attn_fwd", p(qkv), p(out), p(lse2), b, t, h, SCALE, 1, st)
+            K.call("pdnn_flash_attn_fwd", p(qkv), p(out), p(lse2), b, t, h, SCALE, 1, *plain, st)
         with no:
-            K.call("pdnn_flash_attn_bwd", p(qkv), p(out), p(out), p(lse2), p(lse2), p(qkv), b, t, h, SCALE, 1, st)
+            K.call("pdnn_flash_attn_bwd", p(qkv), p(out), p(out), p(lse2), p(lse2), p(qkv), b, t, h, SCALE, 1, *plain, st)
     with no:
-        K.call("pdnn_flash_attn_fwd", p(qkv), p(out), None, B, T, H, SCALE, 1, st)
+        K.call("pdnn_flash_attn_fwd", p(qkv), p(out), None, B, T, H, SCALE, 1, *plain, st)
     with no:
-        K.call("pdnn_flash_attn_bwd", p(qkv), None, p(out), p(lse2), p(lse2), p(qkv), B, T, H, SCALE, 1, st)
+        K.call("pdnn_flash_attn_bwd", p(qkv), None, p(out), p(lse2), p(lse2), p(qkv), B, T, H, SCALE, 1, *plain, st)
     for rows, D in ((0, 64), (-1, 64), (4, 0), (4, 4), (4, 2056)):
         with no:
             K.call("pdnn_layernorm_fwd", p(x), p(g), p(g), p(x), p(v), p(v), rows, D, A.EPS, st)

@@ -38,7 +38,7 @@ def _case(fam, shape, p, lay):
 
 
 def _docs(doc):
-    return (None, None) if doc is None else tuple(t.cuda() for t in doc)
+    return None if doc is None else tuple(t.cuda() for t in doc)
 
 
 # ------------------------------------------------------------------------------------------------ mask export
@@ -105,17 +105,17 @@ def test_attention_dropout_fwd_bwd(shape, fam, p):
     st = _state()
     for lay in [None] + R.LAYOUTS:
         qkv, dO, doc, fwd, Og, lg, bwd = _case(fam, shape, p, lay)
-        q, d0, d1 = qkv.cuda(), *_docs(doc)
-        O, l2 = K.flash_attn_drop_fwd(q, B, T, H, SC, p, st, R.SITE, d0, d1)
+        q, dd, drop = qkv.cuda(), _docs(doc), (p, st, R.SITE)
+        O, l2 = K.flash_attn_fwd(q, B, T, H, SC, doc=dd, drop=drop)
         r = R.check_drop_fwd(O.cpu(), l2.cpu(), fwd, doc)
         # dropout does not touch the softmax: lse2 is the plain (DOC) kernel's, bit for bit
-        l2p = K.flash_attn_fwd(q, B, T, H, SC)[1] if doc is None else K.flash_attn_doc_fwd(q, d0, d1, B, T, H, SC)[1]
+        l2p = K.flash_attn_fwd(q, B, T, H, SC, doc=dd)[1]
         assert A.bits_equal(l2, l2p), (lay, "lse2")
-        O2, _ = K.flash_attn_drop_fwd(q, B, T, H, SC, p, st, R.SITE, d0, d1)
+        O2, _ = K.flash_attn_fwd(q, B, T, H, SC, doc=dd, drop=drop)
         assert A.bits_equal(O, O2), "two calls with one key differ"
-        dqkv = K.flash_attn_drop_bwd(q, Og.cuda(), dO.cuda(), lg.cuda(), B, T, H, SC, p, st, R.SITE, d0, d1)
+        dqkv = K.flash_attn_bwd(q, Og.cuda(), dO.cuda(), lg.cuda(), B, T, H, SC, doc=dd, drop=drop)
         r.update(R.check_drop_bwd(dqkv.cpu(), bwd, B, T, H, doc))
-        assert A.bits_equal(dqkv, K.flash_attn_drop_bwd(q, Og.cuda(), dO.cuda(), lg.cuda(), B, T, H, SC, p, st, R.SITE, d0, d1))
+        assert A.bits_equal(dqkv, K.flash_attn_bwd(q, Og.cuda(), dO.cuda(), lg.cuda(), B, T, H, SC, doc=dd, drop=drop))
         print(shape, fam, p, lay, {k: round(v, 3) for k, v in r.items()})
     assert st.tolist() == list(R.STATE)
 
@@ -129,7 +129,8 @@ def test_attention_dropout_every_backward_variant(wide, delta_in_dq):
         for shape, lay in itertools.product(R.CROSS_SHAPES, (None, "off_edges")):
             B, T, H = shape
             qkv, dO, doc, fwd, Og, lg, bwd = _case("gauss", shape, 0.1, lay)
-            dqkv = K.flash_attn_drop_bwd(qkv.cuda(), Og.cuda(), dO.cuda(), lg.cuda(), B, T, H, SC, 0.1, st, R.SITE, *_docs(doc))
+            dqkv = K.flash_attn_bwd(qkv.cuda(), Og.cuda(), dO.cuda(), lg.cuda(), B, T, H, SC, doc=_docs(doc),
+                                    drop=(0.1, st, R.SITE))
             R.check_drop_bwd(dqkv.cpu(), bwd, B, T, H, doc)
     finally:
         K.tune_set("attn_bwd_wide", old[0])
@@ -142,13 +143,12 @@ def test_p_zero_is_the_plain_and_the_doc_kernel():
     st = _state()
     qkv, dO = (t.cuda() for t in A.gen_flash("gauss", B, T, H))
     for lay in (None, "off_edges"):
-        d0, d1 = _docs(R.doc_of(lay, B, T))
-        O, l2 = K.flash_attn_drop_fwd(qkv, B, T, H, SC, 0.0, st, R.SITE, d0, d1)
-        Op, lp = K.flash_attn_fwd(qkv, B, T, H, SC) if lay is None else K.flash_attn_doc_fwd(qkv, d0, d1, B, T, H, SC)
+        dd = _docs(R.doc_of(lay, B, T))
+        O, l2 = K.flash_attn_fwd(qkv, B, T, H, SC, doc=dd, drop=(0.0, st, R.SITE))
+        Op, lp = K.flash_attn_fwd(qkv, B, T, H, SC, doc=dd)
         assert A.bits_equal(O, Op) and A.bits_equal(l2, lp)
-        g = K.flash_attn_drop_bwd(qkv, O, dO, l2, B, T, H, SC, 0.0, st, R.SITE, d0, d1)
-        gp = (K.flash_attn_bwd(qkv, Op, dO, lp, B, T, H, SC) if lay is None
-              else K.flash_attn_doc_bwd(qkv, Op, dO, lp, d0, d1, B, T, H, SC))
+        g = K.flash_attn_bwd(qkv, O, dO, l2, B, T, H, SC, doc=dd, drop=(0.0, st, R.SITE))
+        gp = K.flash_attn_bwd(qkv, Op, dO, lp, B, T, H, SC, doc=dd)
         assert A.bits_equal(g, gp)
 
 
@@ -157,29 +157,29 @@ def test_wrapper_guards():
     B, T, H = 1, 128, 1
     qkv, dO = (t.cuda() for t in A.gen_flash("gauss", B, T, H))
     st = _state()
-    O, l2 = K.flash_attn_drop_fwd(qkv, B, T, H, SC, 0.1, st, 0)
+    O, l2 = K.flash_attn_fwd(qkv, B, T, H, SC, drop=(0.1, st, 0))
     bad = [dict(p=1.0), dict(p=-0.1), dict(p=float("nan")), dict(state=st.int()), dict(state=st.cpu()),
            dict(state=torch.zeros(3, dtype=torch.int64, device="cuda")), dict(site=-1)]
     for kw in bad:
         a = dict(p=0.1, state=st, site=0)
         a.update(kw)
         with pytest.raises(ValueError):
-            K.flash_attn_drop_fwd(qkv, B, T, H, SC, a["p"], a["state"], a["site"])
+            K.flash_attn_fwd(qkv, B, T, H, SC, drop=(a["p"], a["state"], a["site"]))
         with pytest.raises(ValueError):
-            K.flash_attn_drop_bwd(qkv, O, dO, l2, B, T, H, SC, a["p"], a["state"], a["site"])
+            K.flash_attn_bwd(qkv, O, dO, l2, B, T, H, SC, drop=(a["p"], a["state"], a["site"]))
         x = torch.zeros(2, 8, dtype=A.BF, device="cuda")
         with pytest.raises(ValueError):
             K.dropout_add_fwd(x, None, a["p"], a["state"], a["site"])
     with pytest.raises(ValueError):
-        K.flash_attn_drop_fwd(qkv[:96].contiguous(), 1, 96, 1, SC, 0.1, st, 0)         # T % 128 != 0
+        K.flash_attn_fwd(qkv[:96].contiguous(), 1, 96, 1, SC, drop=(0.1, st, 0))       # T % 128 != 0
     with pytest.raises(ValueError):
-        K.flash_attn_drop_fwd(qkv, B, T, H, SC, 0.1, st, 0, torch.zeros(B, T, dtype=torch.int32, device="cuda"), None)
+        K.flash_attn_fwd(qkv, B, T, H, SC, doc=(torch.zeros(B, T, dtype=torch.int32, device="cuda"), None), drop=(0.1, st, 0))
     with pytest.raises(ValueError):
         K.dropout_add_fwd(torch.zeros(2, 12, dtype=A.BF, device="cuda"), None, 0.1, st, 0)     # D % 8 != 0
     with pytest.raises(ValueError):
         K.dropout_p_eff(1.0)
     # the C entry points refuse a bad p themselves (error return, no launch)
     from pytorch_distributed_nn_amd.ops._backend import lib, ptr, stream
-    assert lib().pdnn_flash_attn_drop_fwd(ptr(qkv), ptr(O), ptr(l2), B, T, H, SC, 1.0, ptr(st), 0, None, None, stream()) != 0
+    assert lib().pdnn_flash_attn_fwd(ptr(qkv), ptr(O), ptr(l2), B, T, H, SC, 1, None, None, 1.0, ptr(st), 0, stream()) != 0
     assert lib().pdnn_dropout_add_fwd(ptr(O), None, ptr(O), B * T, 64, -0.5, ptr(st), 0, stream()) != 0
     torch.cuda.synchronize()

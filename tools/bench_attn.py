@@ -43,12 +43,12 @@ def doc_main(doc_len, rounds):
     ds = (t // doc_len * doc_len).expand(B, T).contiguous()
     de = (ds + doc_len).clamp_max(T).contiguous()
     out, lse = K.flash_attn_fwd(qkv, B, T, H, sc, True)
-    outd, lsed = K.flash_attn_doc_fwd(qkv, ds, de, B, T, H, sc)
+    outd, lsed = K.flash_attn_fwd(qkv, B, T, H, sc, doc=(ds, de))
     do = torch.randn_like(out)
     fns = {"plain_fwd": lambda: K.flash_attn_fwd(qkv, B, T, H, sc, True),
-           "doc_fwd": lambda: K.flash_attn_doc_fwd(qkv, ds, de, B, T, H, sc),
+           "doc_fwd": lambda: K.flash_attn_fwd(qkv, B, T, H, sc, doc=(ds, de)),
            "plain_bwd": lambda: K.flash_attn_bwd(qkv, out, do, lse, B, T, H, sc, True),
-           "doc_bwd": lambda: K.flash_attn_doc_bwd(qkv, outd, do, lsed, ds, de, B, T, H, sc)}
+           "doc_bwd": lambda: K.flash_attn_bwd(qkv, outd, do, lsed, B, T, H, sc, doc=(ds, de))}
     times = {k: [] for k in fns}
     for _ in range(rounds):
         for k, fn in fns.items():
@@ -72,19 +72,19 @@ def drop_main(p, T, doc_len, rounds, bwd_wide):
     if bwd_wide is not None:
         K.tune_set("attn_bwd_wide", bwd_wide)
     qkv = (torch.randn(B * T, 3 * H * 64, device="cuda") * 0.5).to(torch.bfloat16)
-    ds = de = None
+    doc = None
     if doc_len:
         t = torch.arange(T, device="cuda", dtype=torch.int32)
         ds = (t // doc_len * doc_len).expand(B, T).contiguous()
-        de = (ds + doc_len).clamp_max(T).contiguous()
+        doc = (ds, (ds + doc_len).clamp_max(T).contiguous())
     st = torch.tensor([1, 0], dtype=torch.int64, device="cuda")
-    out, lse = K.flash_attn_drop_fwd(qkv, B, T, H, sc, 0.0, st, 0, ds, de)          # p = 0: the plain / DOC entry
-    outd, lsed = K.flash_attn_drop_fwd(qkv, B, T, H, sc, p, st, 0, ds, de)
+    out, lse = K.flash_attn_fwd(qkv, B, T, H, sc, doc=doc, drop=(0.0, st, 0))          # p = 0: the plain / DOC kernels
+    outd, lsed = K.flash_attn_fwd(qkv, B, T, H, sc, doc=doc, drop=(p, st, 0))
     do = torch.randn_like(out)
-    fns = {"base_fwd": lambda: K.flash_attn_drop_fwd(qkv, B, T, H, sc, 0.0, st, 0, ds, de),
-           "drop_fwd": lambda: K.flash_attn_drop_fwd(qkv, B, T, H, sc, p, st, 0, ds, de),
-           "base_bwd": lambda: K.flash_attn_drop_bwd(qkv, out, do, lse, B, T, H, sc, 0.0, st, 0, ds, de),
-           "drop_bwd": lambda: K.flash_attn_drop_bwd(qkv, outd, do, lsed, B, T, H, sc, p, st, 0, ds, de)}
+    fns = {"base_fwd": lambda: K.flash_attn_fwd(qkv, B, T, H, sc, doc=doc, drop=(0.0, st, 0)),
+           "drop_fwd": lambda: K.flash_attn_fwd(qkv, B, T, H, sc, doc=doc, drop=(p, st, 0)),
+           "base_bwd": lambda: K.flash_attn_bwd(qkv, out, do, lse, B, T, H, sc, doc=doc, drop=(0.0, st, 0)),
+           "drop_bwd": lambda: K.flash_attn_bwd(qkv, outd, do, lsed, B, T, H, sc, doc=doc, drop=(p, st, 0))}
     times = {k: [] for k in fns}
     for _ in range(rounds):
         for k, fn in fns.items():
