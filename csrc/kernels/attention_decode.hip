@@ -27,6 +27,20 @@
 // a chunk takes CHUNK / 32 passes; all K and V rows of the chunk are loaded before the first use (the kernel is
 // bandwidth-bound: 2 * 128 bytes per key for 128 FLOPs, fp32 FMAs, no MFMA).
 //
+// pdnn_attn_decode_multi: 1 <= S <= 8 new tokens per sequence in one call (the verify step of speculative decoding).
+// qkv bf16 [B*S][3*H*64], out bf16 [B*S][H*64]; row r = b*S + j is the query at position p_j = lens[b] + j and sees the
+// cache keys 0 .. lens[b]-1 and the new keys of rows b*S .. b*S+j, which come from qkv and never from the cache.  All S new
+// K and V rows go into slots lens[b] .. lens[b]+S-1 (a slot >= Tmax is not stored); lens is not changed.  Same static
+// grid: one block per (b, h, chunk) loads the chunk's K and V once into registers and serves the S queries from them, one
+// after the other (phase 1: the S score rows and their maxima into LDS; phase 2, per query: P, l, o).  Every query's
+// arithmetic is the single-query kernel's (score8 / chunk_tail below are shared, the chunk boundaries are absolute), so
+// out[b*S + j] and the cache slots equal, bit for bit, S successive pdnn_attn_decode calls with lens advanced by one
+// between them.  Partials are indexed by (row r, h, chunk), so the combine kernel runs unchanged over B*S*H blocks; a
+// chunk wholly past p_j writes that query's neutral partial.  No race: cache reads are of slots < lens[b] only, cache
+// writes of slots >= lens[b] only, each by the one block whose chunk holds the slot.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), multi kernel, CHUNK 64 / 128 / 256:
+//   VGPRs 48 / 74 / 129, LDS 10368 / 12416 / 16512 bytes, scratch 0 in every instantiation.
+//
 // pdnn_kv_cache_fill: prefill, the transposing copy of the K and V columns of qkv [B*T][3*H*64] into slots 0..T-1.
 #include "common.h"
 
@@ -34,6 +48,7 @@ namespace {
 constexpr int HD = 64;              // head dim
 constexpr int NTD = 256;            // threads per block
 constexpr int KPP = NTD / 8;        // keys per pass
+constexpr int MAXS = 8;             // most queries per sequence of the multi-query kernel
 constexpr float LOG2E = 1.4426950408889634f;
 
 __device__ __forceinline__ int clamp_len(int p, int Tmax) { return min(max(p, 0), Tmax - 1); }
@@ -44,6 +59,37 @@ __device__ __forceinline__ float sum8(float v) {
     v += dpp_f<0x4E>(v);
     v += dpp_f<0x141>(v);
     return v;
+}
+
+// scaled score of one key for the 8 lanes that share it: q.k in fp32, dims in order, then the 8-lane sum, times c
+__device__ __forceinline__ float score8(const float* q, const u16x8_t& krow, float c) {
+    float kf[8], s = 0.f;
+    unpack8(krow, kf);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s = fmaf(q[e], kf[e], s);
+    return sum8(s) * c;
+}
+
+// the last step of a chunk, by the threads tid < HD (one wave): l = sum of the chunk's P in ascending key order (every
+// lane, same order), o[tid] = sum over the KPP key slots in order; written as the final bf16 row (one chunk) or the partial
+template <int CHUNK>
+__device__ __forceinline__ void chunk_tail(const float* sc, const float (*red)[HD], int tid, float m, bool direct,
+                                           bf16_t* orow, float* po, float* pml) {
+    float l = 0.f;
+#pragma unroll 8
+    for (int j = 0; j < CHUNK; ++j) l += sc[j];
+    float o = 0.f;
+#pragma unroll
+    for (int j = 0; j < KPP; ++j) o += red[j][tid];
+    if (direct) {
+        orow[tid] = f2bf(o / l);
+    } else {
+        po[tid] = o;
+        if (tid == 0) {
+            pml[0] = m;
+            pml[1] = l;
+        }
+    }
 }
 
 template <int CHUNK>
@@ -97,11 +143,7 @@ __global__ void __launch_bounds__(NTD) attn_decode_kernel(const bf16_t* __restri
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
         const int key = k0 + i * KPP + slot;
-        float kf[8], s = 0.f;
-        unpack8(kr[i], kf);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s = fmaf(q[e], kf[e], s);
-        s = sum8(s) * c;
+        float s = score8(q, kr[i], c);
         if (key > p) s = -INFINITY;
         if (sub == 0) sc[i * KPP + slot] = s;
         mx = fmaxf(mx, s);
@@ -123,22 +165,97 @@ __global__ void __launch_bounds__(NTD) attn_decode_kernel(const bf16_t* __restri
     *reinterpret_cast<f32x4_t*>(&red[slot][sub * 8]) = f32x4_t{acc[0], acc[1], acc[2], acc[3]};
     *reinterpret_cast<f32x4_t*>(&red[slot][sub * 8 + 4]) = f32x4_t{acc[4], acc[5], acc[6], acc[7]};
     __syncthreads();
-    if (tid < HD) {                                         // one wave: l (every lane, same order) and o[tid]
-        float l = 0.f;
-#pragma unroll 8
-        for (int j = 0; j < CHUNK; ++j) l += sc[j];
-        float o = 0.f;
+    if (tid < HD) chunk_tail<CHUNK>(sc, red, tid, m, nchunk == 1, out + (long)b * D + h * HD, po, pml);
+}
+
+// S queries per sequence: see the header.  Partial of (row r = b*S + j, h, chunk ch) at index (r*H + h)*nchunk + ch.
+template <int CHUNK>
+__global__ void __launch_bounds__(NTD) attn_decode_multi_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kcache,
+                                                                bf16_t* __restrict__ vcache, const int* __restrict__ lens,
+                                                                bf16_t* __restrict__ out, float* __restrict__ part, int S,
+                                                                int H, int Tmax, int nchunk, float scale) {
+    constexpr int NP = CHUNK / KPP;
+    __shared__ float sc[MAXS][CHUNK];                       // per query: scaled scores, then P
+    __shared__ __attribute__((aligned(16))) float red[KPP][HD];
+    __shared__ float wred[MAXS][NTD / 64];
+    const int tid = threadIdx.x, slot = tid >> 3, sub = tid & 7;
+    const int blk = blockIdx.x, ch = blk % nchunk, bh = blk / nchunk, h = bh % H, b = bh / H;
+    const int p0 = clamp_len(lens[b], Tmax);                // query j sits at p0 + j
+    const int k0 = ch * CHUNK;
+    const int D = H * HD;
+    const long npart = (long)gridDim.x * S;
+    const bf16_t* qrow0 = qkv + (long)b * S * 3 * D + h * HD + sub * 8;
+    bf16_t* Kc = kcache + (long)bh * Tmax * HD + sub * 8;
+    bf16_t* Vc = vcache + (long)bh * Tmax * HD + sub * 8;
+    const u16x8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    u16x8_t kr[NP], vr[NP];
 #pragma unroll
-        for (int j = 0; j < KPP; ++j) o += red[j][tid];
-        if (nchunk == 1) {
-            out[(long)b * D + h * HD + tid] = f2bf(o / l);
-        } else {
-            po[tid] = o;
-            if (tid == 0) {
-                pml[0] = m;
-                pml[1] = l;
+    for (int i = 0; i < NP; ++i) {
+        const int key = k0 + i * KPP + slot;
+        kr[i] = zero;
+        vr[i] = zero;
+        if (key < p0) {
+            kr[i] = *reinterpret_cast<const u16x8_t*>(Kc + (long)key * HD);
+            vr[i] = *reinterpret_cast<const u16x8_t*>(Vc + (long)key * HD);
+        } else if (key - p0 < S) {                          // new token key - p0: from qkv, and into its cache slot
+            const bf16_t* r = qrow0 + (long)(key - p0) * 3 * D;
+            kr[i] = *reinterpret_cast<const u16x8_t*>(r + D);
+            vr[i] = *reinterpret_cast<const u16x8_t*>(r + 2 * D);
+            if (key < Tmax) {
+                *reinterpret_cast<u16x8_t*>(Kc + (long)key * HD) = kr[i];
+                *reinterpret_cast<u16x8_t*>(Vc + (long)key * HD) = vr[i];
             }
         }
+    }
+    const float c = scale * LOG2E;
+    for (int j = 0; j < S; ++j) {                           // phase 1; every branch on j is block-uniform
+        const int p = p0 + j;
+        if (k0 > p) continue;
+        float q[8];
+        unpack8(*reinterpret_cast<const u16x8_t*>(qrow0 + (long)j * 3 * D), q);
+        float mx = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int key = k0 + i * KPP + slot;
+            float s = score8(q, kr[i], c);
+            if (key > p) s = -INFINITY;
+            if (sub == 0) sc[j][i * KPP + slot] = s;
+            mx = fmaxf(mx, s);
+        }
+        mx = wave_max(mx);
+        if ((tid & 63) == 0) wred[j][tid >> 6] = mx;
+    }
+    __syncthreads();
+    for (int j = 0; j < S; ++j) {                           // phase 2
+        const int p = p0 + j;
+        const long pb = ((long)(b * S + j) * H + h) * nchunk + ch;
+        float* po = part + pb * HD;
+        float* pml = part + npart * HD + 2 * pb;
+        if (k0 > p) {                                       // nothing visible to this query in this chunk
+            if (tid < HD) po[tid] = 0.f;
+            if (tid == 0) {
+                pml[0] = -INFINITY;
+                pml[1] = 0.f;
+            }
+            continue;
+        }
+        const float m = fmaxf(fmaxf(wred[j][0], wred[j][1]), fmaxf(wred[j][2], wred[j][3]));
+        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const float pk = __builtin_amdgcn_exp2f(sc[j][i * KPP + slot] - m);
+            if (sub == 0) sc[j][i * KPP + slot] = pk;
+            float vf[8];
+            unpack8(vr[i], vf);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[e] = fmaf(pk, vf[e], acc[e]);
+        }
+        *reinterpret_cast<f32x4_t*>(&red[slot][sub * 8]) = f32x4_t{acc[0], acc[1], acc[2], acc[3]};
+        *reinterpret_cast<f32x4_t*>(&red[slot][sub * 8 + 4]) = f32x4_t{acc[4], acc[5], acc[6], acc[7]};
+        __syncthreads();
+        if (tid < HD)
+            chunk_tail<CHUNK>(sc[j], red, tid, m, nchunk == 1, out + (long)(b * S + j) * D + h * HD, po, pml);
+        __syncthreads();                                    // red is reused by the next query
     }
 }
 
@@ -188,6 +305,16 @@ void launch_decode(const bf16_t* qkv, bf16_t* kcache, bf16_t* vcache, const int*
     if (nchunk > 1)
         hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(B * H), dim3(64), 0, st, (const float*)part, out, nchunk);
 }
+
+template <int CHUNK>
+void launch_decode_multi(const bf16_t* qkv, bf16_t* kcache, bf16_t* vcache, const int* lens, bf16_t* out, float* part,
+                         int B, int S, int H, int Tmax, float scale, hipStream_t st) {
+    const int nchunk = (int)cdiv(Tmax, CHUNK);
+    hipLaunchKernelGGL((attn_decode_multi_kernel<CHUNK>), dim3(B * H * nchunk), dim3(NTD), 0, st, qkv, kcache, vcache,
+                       lens, out, part, S, H, Tmax, nchunk, scale);
+    if (nchunk > 1)
+        hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(B * S * H), dim3(64), 0, st, (const float*)part, out, nchunk);
+}
 }  // namespace
 
 // fp32 elements of the scratch ``part`` that pdnn_attn_decode needs (0 on bad arguments)
@@ -220,5 +347,28 @@ PDNN_API int pdnn_kv_cache_fill(const bf16_t* qkv, bf16_t* kcache, bf16_t* vcach
     const long total = (long)B * H * T * 8;
     hipLaunchKernelGGL(kv_cache_fill_kernel, dim3(stream_grid(total, NTD)), dim3(NTD), 0, st, qkv, kcache, vcache, T, H,
                        Tmax, total);
+    PDNN_LAUNCH_RET;
+}
+
+// fp32 elements of the scratch ``part`` that pdnn_attn_decode_multi needs (0 on bad arguments)
+PDNN_API int pdnn_attn_decode_multi_ws(int B, int S, int H, int Tmax, int chunk) {
+    if (B < 1 || S < 1 || S > MAXS) return 0;
+    const long rows = (long)B * S;
+    return rows > 0x7fffffffL ? 0 : pdnn_attn_decode_ws((int)rows, H, Tmax, chunk);
+}
+
+// qkv [B*S][3*H*64] bf16, kcache / vcache [B][H][Tmax][64] bf16, lens int32 [B] (device), out [B*S][H*64] bf16,
+// part fp32 [pdnn_attn_decode_multi_ws].  1 <= S <= 8, chunk in {64, 128, 256}.
+PDNN_API int pdnn_attn_decode_multi(const bf16_t* qkv, bf16_t* kcache, bf16_t* vcache, const int* lens, bf16_t* out,
+                                    float* part, int B, int S, int H, int Tmax, int chunk, float scale, hipStream_t st) {
+    if (B < 1 || H < 1 || Tmax < 1 || !qkv || !kcache || !vcache || !lens || !out || !part)
+        return (int)hipErrorInvalidValue;
+    if (pdnn_attn_decode_multi_ws(B, S, H, Tmax, chunk) == 0) return (int)hipErrorInvalidValue;
+    if (chunk == 64)
+        launch_decode_multi<64>(qkv, kcache, vcache, lens, out, part, B, S, H, Tmax, scale, st);
+    else if (chunk == 128)
+        launch_decode_multi<128>(qkv, kcache, vcache, lens, out, part, B, S, H, Tmax, scale, st);
+    else
+        launch_decode_multi<256>(qkv, kcache, vcache, lens, out, part, B, S, H, Tmax, scale, st);
     PDNN_LAUNCH_RET;
 }

@@ -146,6 +146,10 @@ _SIGS = {
     "pdnn_doc_bounds": [P, ctypes.c_longlong, P, P, I, I, P],
     "pdnn_attn_decode": [P, P, P, P, P, P, I, I, I, I, F, P],
     "pdnn_attn_decode_ws": [I, I, I, I],
+    "pdnn_attn_decode_multi": [P, P, P, P, P, P, I, I, I, I, I, F, P],
+    "pdnn_attn_decode_multi_ws": [I, I, I, I, I],
+    "pdnn_spec_prepare": [P, I, I, I, P, P, P, ctypes.c_longlong, P, I, I, I, P, P, P, P],
+    "pdnn_spec_accept": [P, P, P, I, I, I, P, P, P, ctypes.c_longlong, P, P, I, I, P],
     "pdnn_kv_cache_fill": [P, P, P, I, I, I, I, P],
     "pdnn_dropout_add_fwd": [P, P, P, L, I, F, P, I, P],
     "pdnn_dropout_bwd": [P, P, L, I, F, P, I, P],

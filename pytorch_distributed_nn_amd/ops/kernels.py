@@ -1566,6 +1566,101 @@ def attn_decode(qkv, kcache, vcache, lens, chunk=DECODE_CHUNK, out=None, part=No
     return out
 
 
+DECODE_MAX_S = 8            # most queries per sequence of attn_decode_multi
+
+
+def attn_decode_multi_ws(B, S, H, Tmax, chunk=DECODE_CHUNK):
+    """fp32 elements of the ``part`` scratch of :func:`attn_decode_multi`"""
+    _chk(chunk in DECODE_CHUNKS, f"attn_decode_multi: chunk must be one of {DECODE_CHUNKS}, got {chunk!r}")
+    _chk(isinstance(S, int) and 1 <= S <= DECODE_MAX_S, f"attn_decode_multi: 1 <= S <= {DECODE_MAX_S}, got S = {S!r}")
+    n = lib().pdnn_attn_decode_multi_ws(B, S, H, Tmax, chunk)
+    _chk(n > 0, f"attn_decode_multi: B={B} S={S} H={H} Tmax={Tmax} chunk={chunk}")
+    return n
+
+
+def attn_decode_multi(qkv, kcache, vcache, lens, S, chunk=DECODE_CHUNK, out=None, part=None, scale=None):
+    """``S`` new tokens per sequence against the cache in one call (1 <= S <= 8), head dim 64: qkv bf16 [B*S][3*H*64],
+    row b*S + j the query at position lens[b] + j, which sees the cache keys 0..lens[b]-1 and the new keys of rows b*S ..
+    b*S+j.  Stores the S new k, v rows into slots lens[b]..lens[b]+S-1 and returns out bf16 [B*S][H*64]; ``lens`` is not
+    changed.  Bit for bit what S successive :func:`attn_decode` calls give with lens advanced by one between them.
+    ``out`` / ``part`` (fp32, >= attn_decode_multi_ws elements) and ``scale`` as for :func:`attn_decode`."""
+    _bf16_c(qkv, "attn_decode_multi.qkv")
+    _chk(isinstance(chunk, int) and chunk in DECODE_CHUNKS,
+         f"attn_decode_multi: chunk must be one of {DECODE_CHUNKS}, got {chunk!r}")
+    _chk(isinstance(S, int) and 1 <= S <= DECODE_MAX_S, f"attn_decode_multi: 1 <= S <= {DECODE_MAX_S}, got S = {S!r}")
+    _cache_chk("attn_decode_multi", kcache, vcache, qkv.device)
+    B, H, Tmax, _ = kcache.shape
+    _chk(qkv.shape == (B * S, 3 * H * 64),
+         f"attn_decode_multi: qkv {tuple(qkv.shape)} for B={B} S={S} H={H}: expected [B*S][3*H*64]")
+    _chk(torch.is_tensor(lens) and lens.dtype == torch.int32 and lens.shape == (B,) and lens.is_contiguous()
+         and lens.device == qkv.device, f"attn_decode_multi: lens must be contiguous int32 [{B}] on {qkv.device}")
+    ws = attn_decode_multi_ws(B, S, H, Tmax, chunk)
+    if out is None:
+        out = torch.empty(B * S, H * 64, device=qkv.device, dtype=BF16)
+    else:
+        _chk(out.dtype == BF16 and out.shape == (B * S, H * 64) and out.is_contiguous() and out.device == qkv.device,
+             f"attn_decode_multi: out must be contiguous bf16 [{B * S}][{H * 64}] on {qkv.device}")
+    if part is None:
+        part = torch.empty(ws, device=qkv.device, dtype=F32)
+    else:
+        _chk(part.dtype == F32 and part.is_contiguous() and part.numel() >= ws and part.device == qkv.device,
+             f"attn_decode_multi: part must be contiguous fp32 with >= {ws} elements on {qkv.device}")
+    call("pdnn_attn_decode_multi", ptr(qkv), ptr(kcache), ptr(vcache), ptr(lens), ptr(out), ptr(part), B, S, H, Tmax,
+         chunk, float(0.125 if scale is None else scale), stream())
+    return out
+
+
+# ----------------------------------------------------------------------------------- speculative decoding (speculate.hip)
+SPEC_MAX_B = 8              # sequences the two bookkeeping kernels take
+
+
+def _spec_chk(name, out, P, N, B, S, vecs):
+    _chk(torch.is_tensor(out) and out.is_cuda and out.dtype == torch.int64 and out.dim() == 2 and out.is_contiguous(),
+         f"{name}: out must be a contiguous CUDA int64 [B][L] tensor")
+    _chk(out.shape[0] == B and 1 <= B <= SPEC_MAX_B and isinstance(S, int) and 1 <= S <= DECODE_MAX_S,
+         f"{name}: 1 <= B <= {SPEC_MAX_B} and 1 <= S <= {DECODE_MAX_S}, got B = {out.shape[0]}, S = {S!r}")
+    _chk(int(P) >= 1 and int(N) >= 1 and int(P) + int(N) <= out.shape[1],
+         f"{name}: P, N >= 1 and P + N <= {out.shape[1]}, got P = {P}, N = {N}")
+    for t, what, dtype, n in vecs:
+        _chk(torch.is_tensor(t) and t.dtype == dtype and t.shape == (n,) and t.is_contiguous() and t.device == out.device,
+             f"{name}: {what} must be contiguous {dtype} [{n}] on out's device")
+
+
+def spec_prepare(out, P, N, prompt_len, ntok, lens, seed, S, tok_in, pos, u, guess=None, ngram=3):
+    """The S input rows of every sequence of a speculative step, one launch (csrc/kernels/speculate.hip;
+    ops.speculate.prepare_reference is the same in torch): ``out`` int64 [B][>= P + N] and ``prompt_len``, ``ntok``,
+    ``lens`` int32 [B] are read; ``tok_in`` int64, ``pos`` int32 and ``u`` fp32 [B*S] are written.  Drafts come from
+    ``guess`` int64 [B][N] when given, else from the n-gram lookup with ``ngram`` >= 1."""
+    B = ntok.numel() if torch.is_tensor(ntok) else 0
+    _spec_chk("spec_prepare", out, P, N, B, S,
+              ((prompt_len, "prompt_len", torch.int32, B), (ntok, "ntok", torch.int32, B), (lens, "lens", torch.int32, B),
+               (tok_in, "tok_in", torch.int64, B * S), (pos, "pos", torch.int32, B * S), (u, "u", F32, B * S)))
+    _chk(isinstance(ngram, int) and ngram >= 1, f"spec_prepare: ngram must be an int >= 1, got {ngram!r}")
+    _chk(guess is None or (torch.is_tensor(guess) and guess.dtype == torch.int64 and guess.shape == (B, int(N))
+                           and guess.is_contiguous() and guess.device == out.device),
+         f"spec_prepare: guess must be contiguous int64 [{B}][{N}] on out's device")
+    call("pdnn_spec_prepare", ptr(out), out.shape[1], int(P), int(N), ptr(prompt_len), ptr(ntok), ptr(lens), int(seed),
+         ptr(guess), ngram, B, S, ptr(tok_in), ptr(pos), ptr(u), stream())
+
+
+def spec_accept(tok_in, t, out, P, N, ntok, lens, done, stats, S, finished=None, eos_token=None):
+    """Accept the drafts that equal the drawn tokens, one launch (ops.speculate.accept_reference is the same in torch):
+    ``tok_in`` and ``t`` int64 [B*S] are read; ``out``, ``ntok``, ``lens`` int32 [B], ``finished`` uint8 [B] (with
+    ``eos_token``), ``done`` int32 [1] and ``stats`` int64 [S+1] are updated."""
+    B = ntok.numel() if torch.is_tensor(ntok) else 0
+    _spec_chk("spec_accept", out, P, N, B, S,
+              ((ntok, "ntok", torch.int32, B), (lens, "lens", torch.int32, B), (tok_in, "tok_in", torch.int64, B * S),
+               (t, "t", torch.int64, B * S), (done, "done", torch.int32, 1), (stats, "stats", torch.int64, S + 1)))
+    _chk((eos_token is None) or (finished is not None and 0 <= int(eos_token) < 2 ** 62),
+         "spec_accept: eos_token needs finished, and must be >= 0")
+    if finished is not None:
+        _chk(torch.is_tensor(finished) and finished.dtype == torch.uint8 and finished.shape == (B,)
+             and finished.is_contiguous() and finished.device == out.device,
+             f"spec_accept: finished must be contiguous uint8 [{B}] on out's device")
+    call("pdnn_spec_accept", ptr(tok_in), ptr(t), ptr(out), out.shape[1], int(P), int(N), ptr(ntok), ptr(lens),
+         ptr(finished), -1 if eos_token is None else int(eos_token), ptr(done), ptr(stats), B, S, stream())
+
+
 def kv_cache_fill(qkv, kcache, vcache, B, T):
     """Prefill: the K and V columns of qkv bf16 [B*T][3*H*64] into slots 0..T-1 of kcache / vcache bf16 [B][H][Tmax][64]
     (T <= Tmax; slots >= T are untouched)."""

@@ -517,10 +517,11 @@ class GPT2BlockFn(torch.autograd.Function):
 class KVCache:
     """The key/value cache of one generation batch on the GPU (csrc/kernels/attention_decode.hip): one K and one V
     allocation bf16 [L][B][H][Tmax][64], ``lens`` int32 [B] on the device (tokens of sequence b already cached; the
-    decode kernels read it there, the host never does) and the fp32 scratch of the split decode kernel.  Slots at or
-    past lens[b] may hold anything, so :meth:`reset` only zeroes ``lens``."""
+    decode kernels read it there, the host never does) and the fp32 scratch of the split decode kernel, sized for ``S``
+    queries per sequence (S > 1: :func:`block_verify`).  Slots at or past lens[b] may hold anything, so :meth:`reset`
+    only zeroes ``lens``."""
 
-    def __init__(self, model, B, Tmax, device, chunk=None):
+    def __init__(self, model, B, Tmax, device, chunk=None, S=1):
         c = model.config
         hd = c.n_embd // c.n_head
         if hd != 64 or c.n_embd % c.n_head:
@@ -528,12 +529,14 @@ class KVCache:
                              f"attention kernel has no other head dim (the CPU path runs any)")
         if B < 1 or Tmax < 1:
             raise ValueError(f"KVCache: B = {B}, Tmax = {Tmax}")
-        self.B, self.H, self.Tmax, self.L = B, c.n_head, Tmax, c.n_layer
+        if not (isinstance(S, int) and 1 <= S <= K.DECODE_MAX_S):
+            raise ValueError(f"KVCache: 1 <= S <= {K.DECODE_MAX_S}, got S = {S!r}")
+        self.B, self.H, self.Tmax, self.L, self.S = B, c.n_head, Tmax, c.n_layer, S
         self.chunk = K.DECODE_CHUNK if chunk is None else chunk
         self.k = torch.zeros(c.n_layer, B, c.n_head, Tmax, 64, device=device, dtype=BF16)
         self.v = torch.zeros_like(self.k)
         self.lens = torch.zeros(B, device=device, dtype=torch.int32)
-        self.part = torch.empty(K.attn_decode_ws(B, c.n_head, Tmax, self.chunk), device=device, dtype=F32)
+        self.part = torch.empty(K.attn_decode_multi_ws(B, S, c.n_head, Tmax, self.chunk), device=device, dtype=F32)
 
     def reset(self):
         self.lens.zero_()
@@ -576,6 +579,27 @@ def block_decode(x, conf, shadows, params, cache, layer):
     ln2, _, _ = K.layernorm_fwd(x1, ln2w, ln2b, eps)
     h = BL.linear_fwd_decode(ln2, wfc, bias=fc_b, act=2)
     return BL.linear_fwd_decode(h, wfc2, bias=fc2_b, res=x1)
+
+
+def block_verify(x, conf, shadows, params, cache, layer, S):
+    """:func:`block_decode` on the S new tokens per sequence of a speculative step: x bf16 [B*S][D] -> x2, row b*S + j
+    at position cache.lens[b] + j, with attn_decode_multi (which also stores the S new k, v rows) in the middle.  The
+    four linears run on K.gemm_skinny for every M = B*S <= K.SKINNY_ROWS, whose row bits do not depend on M: a row gets
+    the bits block_decode gives it."""
+    B, _, H, eps = conf[:4]
+    ln1w, ln1b, _, attn_b, _, proj_b, ln2w, ln2b, _, fc_b, _, fc2_b = params
+    wqkv, wproj, wfc, wfc2 = shadows
+    if S > cache.S or x.shape[0] != B * S or x.shape[0] > K.SKINNY_ROWS:
+        raise ValueError(f"block_verify: {x.shape[0]} rows for B = {B}, S = {S} (cache S = {cache.S}, at most "
+                         f"{K.SKINNY_ROWS} rows)")
+    ln1, _, _ = K.layernorm_fwd(x, ln1w, ln1b, eps)
+    qkv = K.gemm_skinny(ln1, wqkv, bias=attn_b)
+    y = K.attn_decode_multi(qkv, cache.k[layer], cache.v[layer], cache.lens, S, chunk=cache.chunk, part=cache.part,
+                            scale=1.0 / math.sqrt(x.shape[1] // H))
+    x1 = K.gemm_skinny(y, wproj, bias=proj_b, res=x)
+    ln2, _, _ = K.layernorm_fwd(x1, ln2w, ln2b, eps)
+    h = K.gemm_skinny(ln2, wfc, bias=fc_b, act=2)
+    return K.gemm_skinny(h, wfc2, bias=fc2_b, res=x1)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@ random initialisation, with GPT2.generate (key/value cache; on a GPU the decode-
 
     python tools/generate.py --network gpt2_small --checkpoint ckpt.pt --prompt-ids 1,2,3 --max-new-tokens 32
     python tools/generate.py --network gpt2_tiny --random-init --prompt-ids prompt.npy --top-k 40 --seed 1
+    python tools/generate.py --network gpt2_small --random-init --prompt-ids 1,2,3,1,2,3 --sampler device --speculate 4
 
 The prompt is a list of token ids (``1,2,3``) or a .npy file holding an integer vector [P] or matrix [B][P]; there is no
 tokenizer here.  Prints one line of comma-separated ids per row: the prompt followed by the new tokens."""
@@ -51,6 +52,10 @@ def build_parser():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
     ap.add_argument("--graph", action="store_true", help="replay one captured decode step (GPU)")
+    ap.add_argument("--speculate", type=int, default=None, metavar="S",
+                    help="speculative decoding: verify S tokens per step (2..8, needs --sampler device); the tokens are "
+                         "those of the plain loop, and the acceptance statistics go to stderr")
+    ap.add_argument("--draft-ngram", type=int, default=3, metavar="n", help="longest n-gram of the prompt-lookup draft")
     return ap
 
 
@@ -78,11 +83,18 @@ def main(argv=None):
         draw = dict(sampler="device", seed=args.seed)
     else:
         draw = dict(generator=torch.Generator(device=dev).manual_seed(args.seed))
+    if args.speculate is not None:
+        draw.update(speculate=args.speculate, ngram=args.draft_ngram, return_stats=True)
     try:
         out = model.generate(idx.to(dev), args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
                              top_p=args.top_p, eos_token=args.eos_token, graph=args.graph and dev.type == "cuda", **draw)
     except ValueError as e:
         raise SystemExit(str(e))
+    if args.speculate is not None:
+        out, stats = out
+        emitted = sum(e * n for e, n in enumerate(stats["stats"]))
+        print(f"speculate {args.speculate}: {stats['verify_steps']} verify steps, tokens emitted per (row, step) "
+              f"{stats['stats']} (mean {emitted / max(sum(stats['stats']), 1):.2f})", file=sys.stderr)
     for row in out.cpu().tolist():
         print(",".join(map(str, row)))
     return out
