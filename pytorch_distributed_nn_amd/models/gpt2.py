@@ -25,9 +25,9 @@ backward and then advances, so a captured step draws new masks on every replay. 
 on the input's device at the first training forward, seeded from ``torch.initial_seed()`` and the rank; it is no buffer
 and not in ``state_dict``.  The CPU path applies the same bits (``ops.transformer.dropout_keep_reference``).
 
-Generation (``generate``): one prefill over the prompt, then one single-token step per new token against a key/value
-cache (GPU: ``ops.transformer.KVCache`` / ``block_prefill`` / ``block_decode`` on ``csrc/kernels/attention_decode.hip``,
-head dim 64 only; CPU: a plain fp32 cache, the reference of the GPU path).  The document mask is not applied there.
+Generation (``generate``, a delegate to ``generation.py``): one prefill over the prompt, then one single-token step per
+new token against a key/value cache (GPU: ``ops.transformer.KVCache`` / ``block_prefill`` / ``block_step``, head dim 64
+only; CPU: a plain fp32 cache, the reference of the GPU path).  The document mask is not applied there.
 """
 from __future__ import annotations
 
@@ -38,6 +38,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import generation as G
 from .. import tuning
 from ..ops import functional as OF
 from ..ops import transformer as TX
@@ -297,29 +298,14 @@ class GPT2(nn.Module):
         """Tmax of the GPU cache for prompts of P columns: the prefill writes the prompt padded to a multiple of 128"""
         return max((P + 127) // 128 * 128, P + max_new_tokens)
 
-    @staticmethod
-    def _sample(logits, temperature, top_k, generator, top_p=None):
-        """fp32 logits [B][V] -> token ids [B]: argmax for temperature 0 or top_k 1, else temperature, top-k, top-p (a
-        sort: the smallest set of the most probable tokens whose mass reaches top_p), multinomial"""
-        if temperature == 0 or top_k == 1:
-            return logits.argmax(-1)
-        lg = logits / temperature
-        if top_k is not None:
-            kth = torch.topk(lg, min(int(top_k), lg.shape[-1]), dim=-1).values[:, -1:]
-            lg = lg.masked_fill(lg < kth, float("-inf"))
-        if top_p is not None and top_p < 1:
-            sl, si = torch.sort(lg, dim=-1, descending=True)
-            sp = torch.softmax(sl, -1)
-            drop = sp.cumsum(-1) - sp >= top_p                     # the mass before a token already reaches top_p
-            lg = lg.masked_fill(torch.zeros_like(drop).scatter_(-1, si, drop), float("-inf"))
-        return torch.multinomial(torch.softmax(lg, -1), 1, generator=generator).squeeze(1)
+    _sample = staticmethod(G.sample)
 
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, *, temperature=1.0, top_k=None, eos_token=None, prompt_lens=None,
                  generator=None, graph=False, return_logits=False, cache=None, top_p=None, sampler="torch", seed=None,
                  speculate=None, draft="ngram", ngram=3, return_stats=False):
         """Sample ``max_new_tokens`` tokens after the prompts ``idx`` int [B][P] with a key/value cache: one prefill over
-        the prompt, then one single-token step per new token (GPU: ``ops.transformer.block_decode`` on the decode
+        the prompt, then one single-token step per new token (GPU: ``ops.transformer.block_step`` on the decode
         attention kernel of ``csrc/kernels/attention_decode.hip``; CPU: plain PyTorch in fp32 with per-layer k, v lists,
         any head dim, the numerics reference of the GPU path).  Runs under no_grad with evaluation semantics (no dropout)
         and leaves the model as it found it.
@@ -347,7 +333,7 @@ class GPT2(nn.Module):
 
         ``speculate=S`` (2 <= S <= 8; needs ``sampler="device"``): speculative decoding.  One verify step runs the last
         emitted token and S - 1 draft tokens of every row through the model at once (GPU: ``ops.transformer.
-        block_verify`` on the multi-query decode attention kernel, every linear on the skinny GEMM, whose row bits do not
+        block_step`` on the multi-query decode attention kernel, every linear on the skinny GEMM, whose row bits do not
         depend on the row count), draws the target's own token at each of the S positions with u(seed, token index, b),
         and emits the drawn tokens up to and including the first one that differs from its draft.  The returned tokens
         are therefore bit for bit those of ``speculate=None`` with the same seed, whatever the drafts were.  ``draft``:
@@ -360,339 +346,10 @@ class GPT2(nn.Module):
         and Tmax >= kv_cache_len(P, max_new_tokens + S) (rejected drafts occupy slots past the accepted length).
         ``return_logits`` is not available with ``speculate``.  ``return_stats=True`` appends a dict: ``verify_steps``
         and ``stats``, where stats[e] counts the (row, verify step) pairs of incomplete rows that emitted e tokens."""
-        c = self.config
-        if idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
-            raise ValueError(f"generate: idx must be [B][P] with B, P >= 1, got {tuple(idx.shape)}")
-        B, P = idx.shape
-        max_new_tokens = int(max_new_tokens)
-        if max_new_tokens < 0:
-            raise ValueError(f"generate: max_new_tokens must be >= 0, got {max_new_tokens}")
-        if prompt_lens is None:
-            pl = [P] * B
-        else:
-            pl = [int(v) for v in (prompt_lens.tolist() if torch.is_tensor(prompt_lens) else prompt_lens)]
-            if len(pl) != B or min(pl) < 1 or max(pl) > P:
-                raise ValueError(f"generate: prompt_lens must be {B} lengths in [1, {P}], got {pl}")
-        if max(pl) + max_new_tokens > c.block_size:
-            raise ValueError(f"generate: prompt length {max(pl)} + max_new_tokens {max_new_tokens} > block size "
-                             f"{c.block_size}")
-        if temperature < 0 or (top_k is not None and int(top_k) < 1):
-            raise ValueError(f"generate: temperature must be >= 0 and top_k >= 1, got {temperature!r}, {top_k!r}")
-        if top_p is not None and not float(top_p) > 0:
-            raise ValueError(f"generate: top_p must be > 0, got {top_p!r}")
-        if sampler not in ("torch", "device"):
-            raise ValueError(f"generate: sampler must be 'torch' or 'device', got {sampler!r}")
-        if sampler == "device" and (generator is not None or seed is None):
-            raise ValueError("generate: sampler='device' draws from seed: pass seed, and no generator")
-        S = None
-        if speculate is not None:
-            S = int(speculate)
-            if not 2 <= S <= 8:
-                raise ValueError(f"generate: speculate must be in [2, 8], got {speculate!r}")
-            if sampler != "device":
-                raise ValueError("generate: speculate verifies drafts with the counter-based draw: pass sampler='device' "
-                                 "and a seed")
-            if return_logits:
-                raise ValueError("generate: return_logits is not available with speculate")
-            if torch.is_tensor(draft):
-                if draft.dtype != torch.int64 or draft.shape != (B, max_new_tokens):
-                    raise ValueError(f"generate: a draft table must be int64 [{B}][{max_new_tokens}], got {draft.dtype} "
-                                     f"{tuple(draft.shape)}")
-            elif draft != "ngram":
-                raise ValueError(f"generate: draft must be 'ngram' or an int64 [B][max_new_tokens] tensor, got {draft!r}")
-            if not isinstance(ngram, int) or ngram < 1:
-                raise ValueError(f"generate: ngram must be an int >= 1, got {ngram!r}")
-            if idx.is_cuda:
-                from ..ops import kernels as K
-                if not tuning.get("decode_skinny") or B > K.SKINNY_MAX_M or B * S > K.SKINNY_ROWS:
-                    raise ValueError(f"generate: speculate on the GPU needs tuning decode_skinny on, B <= {K.SKINNY_MAX_M} "
-                                     f"and B * S <= {K.SKINNY_ROWS} (the verify rows must get the bits of the plain step's "
-                                     f"skinny GEMM); got decode_skinny = {tuning.get('decode_skinny')!r}, B = {B}, S = {S}")
-        elif return_stats:
-            raise ValueError("generate: return_stats needs speculate")
-        hd = c.n_embd // c.n_head
-        if idx.is_cuda and hd != 64:
-            raise ValueError(f"generation needs the fused kernels (head dim 64); got head dim {hd}: the decode attention "
-                             f"kernel has no other head dim (the CPU path runs any)")
-        idx = idx.long()
-        out = torch.cat([idx, idx.new_zeros(B, max_new_tokens)], 1)
-        if max_new_tokens == 0:
-            if return_stats:
-                return out, {"verify_steps": 0, "stats": [0] * (S + 1)}
-            return (out, torch.empty(B, 0, c.vocab_size, device=idx.device)) if return_logits else out
-        pl_dev = torch.tensor(pl, device=idx.device, dtype=torch.int32)
-        if sampler == "device":
-            draw = dict(temperature=float(temperature), top_k=top_k, top_p=top_p, eos_token=eos_token)
-            seed = int(seed) & ((1 << 63) - 1)
-            if S is not None:
-                guess = draft.to(idx.device).contiguous() if torch.is_tensor(draft) else None
-                spec = (S, guess, ngram)
-                if idx.is_cuda:
-                    stats = self._generate_fused(idx, pl_dev, max_new_tokens, graph, cache,
-                                                 device_sampler=(out, draw, seed, False), spec=spec)
-                else:
-                    stats = self._speculate_reference(idx, pl_dev, max_new_tokens, out, draw, seed, spec)
-                return (out, stats) if return_stats else out
-            if idx.is_cuda:
-                kept = self._generate_fused(idx, pl_dev, max_new_tokens, graph, cache,
-                                            device_sampler=(out, draw, seed, return_logits))
-                return (out, kept) if return_logits else out
-            from ..ops.sampling import sample_reference
-            logits, step = self._generate_reference(idx, pl_dev, max(pl) + max_new_tokens)
-            finished = torch.zeros(B, dtype=torch.uint8) if eos_token is not None else None
-            kept = []
-            for i in range(max_new_tokens):
-                if return_logits:
-                    kept.append(logits.clone())
-                tok, _, _ = sample_reference(logits, state=(seed, i), finished=finished, **draw)
-                out[:, P + i] = tok
-                if i + 1 < max_new_tokens:
-                    logits = step(tok)
-            return (out, torch.stack(kept, 1)) if return_logits else out
-        if idx.is_cuda:
-            logits, step = self._generate_fused(idx, pl_dev, max_new_tokens, graph, cache)
-        else:
-            logits, step = self._generate_reference(idx, pl_dev, max(pl) + max_new_tokens)
-        finished = torch.zeros(B, dtype=torch.bool, device=idx.device)
-        kept = []
-        for i in range(max_new_tokens):
-            if return_logits:
-                kept.append(logits.clone())
-            tok = self._sample(logits, temperature, top_k, generator, top_p)
-            if eos_token is not None:
-                tok = torch.where(finished, torch.full_like(tok, int(eos_token)), tok)
-                finished = finished | (tok == int(eos_token))
-            out[:, P + i] = tok
-            if i + 1 < max_new_tokens:
-                logits = step(tok)
-        return (out, torch.stack(kept, 1)) if return_logits else out
-
-    def _generate_fused(self, idx, pl_dev, max_new_tokens, graph, cache, device_sampler=None, spec=None):
-        """GPU: prefill -> (fp32 logits [B][V] at each prompt's last position, step(tok) -> the next logits).  With
-        ``device_sampler`` = (out, draw arguments, seed, return_logits) the whole loop runs here on the sampling kernel
-        and the result is the kept fp32 logits [B][N][V] (or None); with ``spec`` = (S, guess, ngram) too it is the
-        speculative loop and the result is its statistics."""
-        c, tr = self.config, self.transformer
-        B, P = idx.shape
-        Tp = (P + 127) // 128 * 128                  # right-padded: causality keeps the padding invisible to real positions
-        S = 1 if spec is None else spec[0]
-        Tneed = self.kv_cache_len(P, max_new_tokens + (S if spec is not None else 0))
-        if cache is None:
-            cache = TX.KVCache(self, B, Tneed, idx.device, S=S)
-        elif cache.B != B or cache.Tmax < Tneed or cache.k.device != idx.device or cache.S < S:
-            raise ValueError(f"generate: cache of B = {cache.B}, Tmax = {cache.Tmax}, S = {cache.S} on {cache.k.device} does "
-                             f"not fit B = {B}, Tmax >= {Tneed}, S >= {S} on {idx.device}")
-        cache.reset()
-        wte_k, wpe_k = OF.weight_bf16(tr.wte.weight), OF.weight_bf16(tr.wpe.weight)
-        blocks = [blk.fused_params() for blk in tr.h]
-        lnw, lnb = tr.ln_f.weight, tr.ln_f.bias
-        # prefill: positions past the table are clamped to its last row
-        wpe_p = wpe_k if Tp <= c.block_size else torch.cat([wpe_k, wpe_k[-1:].expand(Tp - c.block_size, -1)]).contiguous()
-        from ..ops import kernels as K
-        x = K.embedding_fwd(F.pad(idx, (0, Tp - P)).reshape(-1).contiguous(), wte_k, wpe_p, Tp)
-        for layer, (params, shadows) in enumerate(blocks):
-            x = TX.block_prefill(x, (B, Tp, c.n_head, c.eps), shadows, params, cache, layer)
-        rows = torch.arange(B, device=idx.device) * Tp + pl_dev.long() - 1
-        xf, _, _ = K.layernorm_fwd(x.index_select(0, rows), lnw, lnb, c.eps)
-        logits16 = TX.BL.linear_fwd_decode(xf, wte_k)
-        cache.lens.copy_(pl_dev)
-        tok_buf = torch.zeros(B, dtype=torch.int64, device=idx.device)
-        if spec is not None:
-            return self._speculate_loop_device(logits16, tok_buf, cache, wte_k, wpe_k, blocks, pl_dev, P, max_new_tokens,
-                                               graph, *device_sampler[:3], *spec)
-        if device_sampler is not None:
-            return self._decode_loop_device(logits16, tok_buf, cache, wte_k, wpe_k, blocks, P, max_new_tokens, graph,
-                                            *device_sampler)
-        logits = logits16.float()
-        logit_buf = torch.empty_like(logits)
-
-        def one_step():     # tok_buf -> logit_buf; no host read-back, no side stream: capturable as it stands
-            x = K.embedding_decode(tok_buf, cache.lens, wte_k, wpe_k)     # position min(lens[b], block_size - 1)
-            for layer, (params, shadows) in enumerate(blocks):
-                x = TX.block_decode(x, (B, 1, c.n_head, c.eps), shadows, params, cache, layer)
-            xf, _, _ = K.layernorm_fwd(x, lnw, lnb, c.eps)
-            logit_buf.copy_(TX.BL.linear_fwd_decode(xf, wte_k))
-            cache.lens.add_(1)
-
-        state = {"n": 0, "graph": None}
-
-        def step(tok):
-            tok_buf.copy_(tok)
-            if not graph or state["n"] == 0:            # eager, and the warm-up step of graph=True
-                one_step()
-            else:
-                if state["graph"] is None:
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        one_step()
-                    state["graph"] = g
-                state["graph"].replay()
-            state["n"] += 1
-            return logit_buf
-        return logits, step
-
-    def _decode_loop_device(self, logit_buf, tok_buf, cache, wte_k, wpe_k, blocks, P, N, graph, out, draw, seed, keep):
-        """The decode loop with the sampling kernel inside the step.  One unit: sample from the bf16 ``logit_buf`` into
-        ``tok_buf``, column P + step of ``out`` and the eos flags; embedding -> blocks -> ln_f -> LM head into
-        ``logit_buf``; lens += 1, step += 1.  Nothing is read back and nothing runs on a side stream, so the unit is
-        capturable as it stands; the last token needs no forward and is sampled alone."""
-        from ..ops import kernels as K
-        c, tr = self.config, self.transformer
-        B, dev = tok_buf.numel(), tok_buf.device
-        lnw, lnb = tr.ln_f.weight, tr.ln_f.bias
-        state = torch.tensor([seed, 0], dtype=torch.int64, device=dev)
-        one = torch.tensor([0, 1], dtype=torch.int64, device=dev)
-        eos = draw["eos_token"]
-        finished = torch.zeros(B, dtype=torch.uint8, device=dev) if eos is not None else None
-
-        def sample():
-            K.sample_logits(logit_buf, tok_buf, state, temperature=draw["temperature"], top_k=draw["top_k"],
-                            top_p=draw["top_p"], history=out, col0=P, finished=finished, eos_token=eos)
-
-        def unit():
-            sample()
-            x = K.embedding_decode(tok_buf, cache.lens, wte_k, wpe_k)
-            for layer, (params, shadows) in enumerate(blocks):
-                x = TX.block_decode(x, (B, 1, c.n_head, c.eps), shadows, params, cache, layer)
-            xf, _, _ = K.layernorm_fwd(x, lnw, lnb, c.eps)
-            logit_buf.copy_(TX.BL.linear_fwd_decode(xf, wte_k))
-            cache.lens.add_(1)
-            state.add_(one)
-
-        kept, g = [], None
-        for i in range(N):
-            if keep:
-                kept.append(logit_buf.float())
-            if i == N - 1:
-                sample()
-            elif not graph or i == 0:                   # eager, and the warm-up step of graph=True
-                unit()
-            else:
-                if g is None:
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        unit()
-                g.replay()
-        return torch.stack(kept, 1) if keep else None
-
-    def _speculate_loop_device(self, logit_buf, tok_buf, cache, wte_k, wpe_k, blocks, pl_dev, P, N, graph, out, draw, seed,
-                               S, guess, ngram):
-        """The speculative loop.  Token 0 is drawn from the prefill logits as in :meth:`_decode_loop_device`; then one
-        unit per verify step: spec_prepare (last token + S - 1 drafts, positions, the uniforms of token indices ntok ..
-        ntok + S - 1) -> embedding -> block_verify x L -> ln_f -> LM head (skinny GEMM, B*S rows) -> sample with those
-        uniforms -> spec_accept (out, ntok, lens, the eos flags, done, stats).  One stream, nothing allocated after the
-        warm-up unit, so it is captured as it stands; the host reads ``done`` after each unit."""
-        from ..ops import kernels as K
-        c, tr = self.config, self.transformer
-        B, dev = tok_buf.numel(), tok_buf.device
-        R = B * S
-        lnw, lnb = tr.ln_f.weight, tr.ln_f.bias
-        state = torch.tensor([seed, 0], dtype=torch.int64, device=dev)
-        eos = draw["eos_token"]
-        finished = torch.zeros(B, dtype=torch.uint8, device=dev) if eos is not None else None
-        kw = dict(temperature=draw["temperature"], top_k=draw["top_k"], top_p=draw["top_p"])
-        K.sample_logits(logit_buf, tok_buf, state, history=out, col0=P, finished=finished, eos_token=eos, **kw)
-        ntok = torch.ones(B, dtype=torch.int32, device=dev)
-        tok_in = torch.zeros(R, dtype=torch.int64, device=dev)
-        t = torch.zeros_like(tok_in)
-        pos = torch.zeros(R, dtype=torch.int32, device=dev)
-        u = torch.zeros(R, dtype=torch.float32, device=dev)
-        done = torch.zeros(1, dtype=torch.int32, device=dev)
-        stats = torch.zeros(S + 1, dtype=torch.int64, device=dev)
-
-        def unit():
-            K.spec_prepare(out, P, N, pl_dev, ntok, cache.lens, seed, S, tok_in, pos, u, guess=guess, ngram=ngram)
-            x = K.embedding_decode(tok_in, pos, wte_k, wpe_k)
-            for layer, (params, shadows) in enumerate(blocks):
-                x = TX.block_verify(x, (B, S, c.n_head, c.eps), shadows, params, cache, layer, S)
-            xf, _, _ = K.layernorm_fwd(x, lnw, lnb, c.eps)
-            K.sample_logits(K.gemm_skinny(xf, wte_k), t, state, u=u, **kw)
-            K.spec_accept(tok_in, t, out, P, N, ntok, cache.lens, done, stats, S, finished=finished, eos_token=eos)
-
-        g, steps = None, 0
-        while steps < N - 1:
-            if not graph or steps == 0:                 # eager, and the warm-up unit of graph=True
-                unit()
-            else:
-                if g is None:
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        unit()
-                g.replay()
-            steps += 1
-            if int(done.item()):
-                break
-        return {"verify_steps": steps, "stats": stats.tolist()}
-
-    def _speculate_reference(self, idx, pl_dev, N, out, draw, seed, spec):
-        """CPU: the same draft / verify / accept loop on ops.speculate's references.  The S verify logits of a step come
-        from S successive single-token reference steps (a position the row never reaches is clamped to the last slot,
-        which no emitted token reads); the cache length is then set to the accepted prefix."""
-        from ..ops.sampling import sample_reference
-        from ..ops.speculate import accept_reference, prepare_reference
-        S, guess, ngram = spec
-        B, P = idx.shape
-        Tmax = int(pl_dev.max()) + N
-        logits, step = self._generate_reference(idx, pl_dev, Tmax)
-        eos = draw["eos_token"]
-        finished = torch.zeros(B, dtype=torch.uint8, device=idx.device) if eos is not None else None
-        tok, _, _ = sample_reference(logits, state=(seed, 0), finished=finished, **draw)
-        out[:, P] = tok
-        kw = dict(temperature=draw["temperature"], top_k=draw["top_k"], top_p=draw["top_p"])
-        ntok = torch.ones(B, dtype=torch.int32, device=idx.device)
-        lens = pl_dev.clone()
-        stats = torch.zeros(S + 1, dtype=torch.int64)
-        steps = 0
-        while steps < N - 1:
-            tok_in, _, u = prepare_reference(out, P, N, pl_dev, ntok, lens, seed, S, guess=guess, ngram=ngram)
-            t = torch.zeros_like(tok_in)
-            for j in range(S):
-                step.lens.copy_((lens.long() + j).clamp(max=Tmax - 1))
-                t[j::S], _, _ = sample_reference(step(tok_in[j::S]), u=u[j::S], **kw)
-            done = accept_reference(tok_in, t, out, P, N, ntok, lens, finished, eos, stats, S)
-            step.lens.copy_(lens)
-            steps += 1
-            if done:
-                break
-        return {"verify_steps": steps, "stats": stats.tolist()}
-
-    def _generate_reference(self, idx, pl_dev, Tmax):
-        """CPU (any device, plain PyTorch, fp32): the same prefill + cached steps with per-layer k, v lists"""
-        c, tr = self.config, self.transformer
-        B, P = idx.shape
-        H, hd = c.n_head, c.n_embd // c.n_head
-        dev = idx.device
-        ks = [torch.zeros(B, H, Tmax, hd, device=dev, dtype=tr.wte.weight.dtype) for _ in tr.h]
-        vs = [torch.zeros_like(k) for k in ks]
-        lens = pl_dev.long().clone()
-        ar = torch.arange(B, device=dev)
-
-        def heads(t, T):
-            return t.view(B, T, H, hd).transpose(1, 2)
-
-        x = tr.wte(idx) + tr.wpe(torch.arange(P, device=dev).clamp(max=c.block_size - 1))
-        for blk, kc, vc in zip(tr.h, ks, vs):
-            q, k, v = (heads(t, P) for t in blk.attn.c_attn(blk.ln_1(x)).split(c.n_embd, dim=2))
-            kc[:, :, :P], vc[:, :, :P] = k, v
-            y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
-            x = x + blk.attn.c_proj(y.transpose(1, 2).reshape(B, P, c.n_embd))
-            x = x + blk.mlp(blk.ln_2(x))
-        logits = self.lm_head(tr.ln_f(x[ar, lens - 1])).float()
-        keys = torch.arange(Tmax, device=dev)
-
-        def step(tok):
-            x = tr.wte(tok) + tr.wpe(lens.clamp(max=c.block_size - 1))                 # [B][D]
-            vis = (keys[None, :] <= lens[:, None])[:, None, None, :]                    # keys 0..lens[b], new one included
-            for blk, kc, vc in zip(tr.h, ks, vs):
-                q, k, v = (t.view(B, H, hd) for t in blk.attn.c_attn(blk.ln_1(x)).split(c.n_embd, dim=1))
-                kc[ar, :, lens], vc[ar, :, lens] = k, v
-                y = F.scaled_dot_product_attention(q.unsqueeze(2), kc, vc, attn_mask=vis)
-                x = x + blk.attn.c_proj(y.reshape(B, c.n_embd))
-                x = x + blk.mlp(blk.ln_2(x))
-            lens.add_(1)
-            return self.lm_head(tr.ln_f(x)).float()
-        step.lens = lens                                # the speculative loop sets the length back after a verify step
-        return logits, step
+        return G.generate(self, idx, max_new_tokens, temperature=temperature, top_k=top_k, eos_token=eos_token,
+                          prompt_lens=prompt_lens, generator=generator, graph=graph, return_logits=return_logits,
+                          cache=cache, top_p=top_p, sampler=sampler, seed=seed, speculate=speculate, draft=draft,
+                          ngram=ngram, return_stats=return_stats)
 
     def _forward_reference(self, idx, targets=None, doc=None, drop=None):
         B, T = idx.shape

@@ -1529,6 +1529,36 @@ def _cache_chk(name, kcache, vcache, dev):
          f"{name}: kcache {tuple(kcache.shape)} and vcache {tuple(vcache.shape)} must have one non-empty shape")
 
 
+def _attn_decode(name, sym, S, qkv, kcache, vcache, lens, chunk, out, part, scale):
+    """The checks and the launch of :func:`attn_decode` (``S`` None: its C entry takes none) and :func:`attn_decode_multi`"""
+    _bf16_c(qkv, f"{name}.qkv")
+    _chk(isinstance(chunk, int) and chunk in DECODE_CHUNKS, f"{name}: chunk must be one of {DECODE_CHUNKS}, got {chunk!r}")
+    _chk(S is None or (isinstance(S, int) and 1 <= S <= DECODE_MAX_S), f"{name}: 1 <= S <= {DECODE_MAX_S}, got S = {S!r}")
+    _cache_chk(name, kcache, vcache, qkv.device)
+    B, H, Tmax, _ = kcache.shape
+    if S is None:
+        R, per, want = B, (), f"B={B} H={H}: expected [B][3*H*64]"
+    else:
+        R, per, want = B * S, (S,), f"B={B} S={S} H={H}: expected [B*S][3*H*64]"
+    _chk(qkv.shape == (R, 3 * H * 64), f"{name}: qkv {tuple(qkv.shape)} for {want}")
+    _chk(torch.is_tensor(lens) and lens.dtype == torch.int32 and lens.shape == (B,) and lens.is_contiguous()
+         and lens.device == qkv.device, f"{name}: lens must be contiguous int32 [{B}] on {qkv.device}")
+    ws = attn_decode_ws(B, H, Tmax, chunk) if S is None else attn_decode_multi_ws(B, S, H, Tmax, chunk)
+    if out is None:
+        out = torch.empty(R, H * 64, device=qkv.device, dtype=BF16)
+    else:
+        _chk(out.dtype == BF16 and out.shape == (R, H * 64) and out.is_contiguous() and out.device == qkv.device,
+             f"{name}: out must be contiguous bf16 [{R}][{H * 64}] on {qkv.device}")
+    if part is None:
+        part = torch.empty(ws, device=qkv.device, dtype=F32)
+    else:
+        _chk(part.dtype == F32 and part.is_contiguous() and part.numel() >= ws and part.device == qkv.device,
+             f"{name}: part must be contiguous fp32 with >= {ws} elements on {qkv.device}")
+    call(sym, ptr(qkv), ptr(kcache), ptr(vcache), ptr(lens), ptr(out), ptr(part), B, *per, H, Tmax, chunk,
+         float(0.125 if scale is None else scale), stream())
+    return out
+
+
 def attn_decode_ws(B, H, Tmax, chunk=DECODE_CHUNK):
     """fp32 elements of the ``part`` scratch of :func:`attn_decode`"""
     _chk(chunk in DECODE_CHUNKS, f"attn_decode: chunk must be one of {DECODE_CHUNKS}, got {chunk!r}")
@@ -1543,27 +1573,7 @@ def attn_decode(qkv, kcache, vcache, lens, chunk=DECODE_CHUNK, out=None, part=No
     Stores the new k, v rows into slot lens[b] and returns out bf16 [B][H*64] = softmax over keys 0..lens[b] times V.
     ``lens`` is not changed.  ``out`` / ``part`` (fp32, >= attn_decode_ws elements): preallocated buffers, so that a
     captured step allocates nothing.  ``scale`` defaults to 1 / 8."""
-    _bf16_c(qkv, "attn_decode.qkv")
-    _chk(isinstance(chunk, int) and chunk in DECODE_CHUNKS, f"attn_decode: chunk must be one of {DECODE_CHUNKS}, got {chunk!r}")
-    _cache_chk("attn_decode", kcache, vcache, qkv.device)
-    B, H, Tmax, _ = kcache.shape
-    _chk(qkv.shape == (B, 3 * H * 64), f"attn_decode: qkv {tuple(qkv.shape)} for B={B} H={H}: expected [B][3*H*64]")
-    _chk(torch.is_tensor(lens) and lens.dtype == torch.int32 and lens.shape == (B,) and lens.is_contiguous()
-         and lens.device == qkv.device, f"attn_decode: lens must be contiguous int32 [{B}] on {qkv.device}")
-    ws = attn_decode_ws(B, H, Tmax, chunk)
-    if out is None:
-        out = torch.empty(B, H * 64, device=qkv.device, dtype=BF16)
-    else:
-        _chk(out.dtype == BF16 and out.shape == (B, H * 64) and out.is_contiguous() and out.device == qkv.device,
-             f"attn_decode: out must be contiguous bf16 [{B}][{H * 64}] on {qkv.device}")
-    if part is None:
-        part = torch.empty(ws, device=qkv.device, dtype=F32)
-    else:
-        _chk(part.dtype == F32 and part.is_contiguous() and part.numel() >= ws and part.device == qkv.device,
-             f"attn_decode: part must be contiguous fp32 with >= {ws} elements on {qkv.device}")
-    call("pdnn_attn_decode", ptr(qkv), ptr(kcache), ptr(vcache), ptr(lens), ptr(out), ptr(part), B, H, Tmax, chunk,
-         float(0.125 if scale is None else scale), stream())
-    return out
+    return _attn_decode("attn_decode", "pdnn_attn_decode", None, qkv, kcache, vcache, lens, chunk, out, part, scale)
 
 
 DECODE_MAX_S = 8            # most queries per sequence of attn_decode_multi
@@ -1584,30 +1594,8 @@ def attn_decode_multi(qkv, kcache, vcache, lens, S, chunk=DECODE_CHUNK, out=None
     b*S+j.  Stores the S new k, v rows into slots lens[b]..lens[b]+S-1 and returns out bf16 [B*S][H*64]; ``lens`` is not
     changed.  Bit for bit what S successive :func:`attn_decode` calls give with lens advanced by one between them.
     ``out`` / ``part`` (fp32, >= attn_decode_multi_ws elements) and ``scale`` as for :func:`attn_decode`."""
-    _bf16_c(qkv, "attn_decode_multi.qkv")
-    _chk(isinstance(chunk, int) and chunk in DECODE_CHUNKS,
-         f"attn_decode_multi: chunk must be one of {DECODE_CHUNKS}, got {chunk!r}")
-    _chk(isinstance(S, int) and 1 <= S <= DECODE_MAX_S, f"attn_decode_multi: 1 <= S <= {DECODE_MAX_S}, got S = {S!r}")
-    _cache_chk("attn_decode_multi", kcache, vcache, qkv.device)
-    B, H, Tmax, _ = kcache.shape
-    _chk(qkv.shape == (B * S, 3 * H * 64),
-         f"attn_decode_multi: qkv {tuple(qkv.shape)} for B={B} S={S} H={H}: expected [B*S][3*H*64]")
-    _chk(torch.is_tensor(lens) and lens.dtype == torch.int32 and lens.shape == (B,) and lens.is_contiguous()
-         and lens.device == qkv.device, f"attn_decode_multi: lens must be contiguous int32 [{B}] on {qkv.device}")
-    ws = attn_decode_multi_ws(B, S, H, Tmax, chunk)
-    if out is None:
-        out = torch.empty(B * S, H * 64, device=qkv.device, dtype=BF16)
-    else:
-        _chk(out.dtype == BF16 and out.shape == (B * S, H * 64) and out.is_contiguous() and out.device == qkv.device,
-             f"attn_decode_multi: out must be contiguous bf16 [{B * S}][{H * 64}] on {qkv.device}")
-    if part is None:
-        part = torch.empty(ws, device=qkv.device, dtype=F32)
-    else:
-        _chk(part.dtype == F32 and part.is_contiguous() and part.numel() >= ws and part.device == qkv.device,
-             f"attn_decode_multi: part must be contiguous fp32 with >= {ws} elements on {qkv.device}")
-    call("pdnn_attn_decode_multi", ptr(qkv), ptr(kcache), ptr(vcache), ptr(lens), ptr(out), ptr(part), B, S, H, Tmax,
-         chunk, float(0.125 if scale is None else scale), stream())
-    return out
+    return _attn_decode("attn_decode_multi", "pdnn_attn_decode_multi", S, qkv, kcache, vcache, lens, chunk, out, part,
+                        scale)
 
 
 # ----------------------------------------------------------------------------------- speculative decoding (speculate.hip)

@@ -512,21 +512,18 @@ class GPT2BlockFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------
-# inference: key/value cache, prefill and single-token decode blocks (plain functions, no autograd)
+# inference: key/value cache, prefill and decode-step blocks (plain functions, no autograd)
 # ------------------------------------------------------------------------------------------------
 class KVCache:
     """The key/value cache of one generation batch on the GPU (csrc/kernels/attention_decode.hip): one K and one V
     allocation bf16 [L][B][H][Tmax][64], ``lens`` int32 [B] on the device (tokens of sequence b already cached; the
     decode kernels read it there, the host never does) and the fp32 scratch of the split decode kernel, sized for ``S``
-    queries per sequence (S > 1: :func:`block_verify`).  Slots at or past lens[b] may hold anything, so :meth:`reset`
+    queries per sequence (S > 1: :func:`block_step`).  Slots at or past lens[b] may hold anything, so :meth:`reset`
     only zeroes ``lens``."""
 
     def __init__(self, model, B, Tmax, device, chunk=None, S=1):
         c = model.config
-        hd = c.n_embd // c.n_head
-        if hd != 64 or c.n_embd % c.n_head:
-            raise ValueError(f"generation needs the fused kernels (head dim 64); got head dim {hd}: the decode "
-                             f"attention kernel has no other head dim (the CPU path runs any)")
+        need_fused_kernels(c.n_embd, c.n_head)
         if B < 1 or Tmax < 1:
             raise ValueError(f"KVCache: B = {B}, Tmax = {Tmax}")
         if not (isinstance(S, int) and 1 <= S <= K.DECODE_MAX_S):
@@ -542,64 +539,58 @@ class KVCache:
         self.lens.zero_()
 
 
+def need_fused_kernels(D, H, T=None):
+    """Generation runs on the head-dim-64 kernels only, a prefill (``T`` given) on the flash kernels (:func:`use_flash`)"""
+    hd = D // H
+    if hd == 64 and D % H == 0 and (T is None or T % 128 == 0):
+        return
+    if T is not None:
+        raise ValueError(f"generation needs the fused kernels (head dim 64, T % 128 == 0); got head dim {hd}, T = {T}")
+    raise ValueError(f"generation needs the fused kernels (head dim 64); got head dim {hd}: the decode attention kernel "
+                     f"has no other head dim (the CPU path runs any)")
+
+
+def _block_infer(x, eps, shadows, params, lin, attn, *args, **kw):
+    """The forward kernel sequence of :class:`GPT2BlockFn` with nothing saved, x bf16 [rows][D] -> x2: ``lin`` is the
+    linear of the four GEMMs, ``attn(qkv, *args, **kw)`` takes the packed qkv to the attention output."""
+    ln1w, ln1b, _, attn_b, _, proj_b, ln2w, ln2b, _, fc_b, _, fc2_b = params
+    wqkv, wproj, wfc, wfc2 = shadows
+    ln1, _, _ = K.layernorm_fwd(x, ln1w, ln1b, eps)
+    y = attn(lin(ln1, wqkv, bias=attn_b), *args, **kw)
+    x1 = lin(y, wproj, bias=proj_b, res=x)
+    ln2, _, _ = K.layernorm_fwd(x1, ln2w, ln2b, eps)
+    h = lin(ln2, wfc, bias=fc_b, act=2)
+    return lin(h, wfc2, bias=fc2_b, res=x1)
+
+
 def block_prefill(x, conf, shadows, params, cache, layer):
-    """One block over the whole (padded) prompt, the forward kernel sequence of :class:`GPT2BlockFn` with nothing saved:
-    x bf16 [B*T][D], conf = (B, T, H, eps) or a :class:`BlockConf`, T % 128 == 0 -> x2; the K and V of every position
-    also go into slots 0..T-1 of ``cache`` layer ``layer``.  The linears are bf16 (BL.linear_fwd) whatever config.fp8
-    says."""
+    """One block over the whole (padded) prompt: x bf16 [B*T][D], conf = (B, T, H, eps) or a :class:`BlockConf`,
+    T % 128 == 0 -> x2; the K and V of every position also go into slots 0..T-1 of ``cache`` layer ``layer``.  The
+    linears are bf16 (BL.linear_fwd) whatever config.fp8 says."""
     B, T, H, eps = conf[:4]
-    ln1w, ln1b, _, attn_b, _, proj_b, ln2w, ln2b, _, fc_b, _, fc2_b = params
-    wqkv, wproj, wfc, wfc2 = shadows
-    attn = _BlockAttn(BlockConf(B, T, H, eps), x.shape[1])          # a prompt is one document, and nothing is dropped
-    if not attn.flash:
-        raise ValueError(f"generation needs the fused kernels (head dim 64, T % 128 == 0); got head dim "
-                         f"{x.shape[1] // H}, T = {T}")
-    ln1, _, _ = K.layernorm_fwd(x, ln1w, ln1b, eps)
-    qkv = BL.linear_fwd(ln1, wqkv, bias=attn_b)
-    K.kv_cache_fill(qkv, cache.k[layer], cache.v[layer], B, T)
-    y, _, _ = attn.fwd(qkv)
-    x1 = BL.linear_fwd(y, wproj, bias=proj_b, res=x)
-    ln2, _, _ = K.layernorm_fwd(x1, ln2w, ln2b, eps)
-    h = BL.linear_fwd(ln2, wfc, bias=fc_b, act=2)
-    return BL.linear_fwd(h, wfc2, bias=fc2_b, res=x1)
+    need_fused_kernels(x.shape[1], H, T)
+
+    def attn(qkv):      # a prompt is one document, and nothing is dropped
+        K.kv_cache_fill(qkv, cache.k[layer], cache.v[layer], B, T)
+        return K.flash_attn_fwd(qkv, B, T, H, 1.0 / math.sqrt(x.shape[1] // H))[0]
+    return _block_infer(x, eps, shadows, params, BL.linear_fwd, attn)
 
 
-def block_decode(x, conf, shadows, params, cache, layer):
-    """One block on the one new token per sequence: x bf16 [B][D] -> x2, with attn_decode (which also stores the new
-    k, v into slot cache.lens[b]) in the middle; the four linears have M = B rows (BL.linear_fwd_decode).  Nothing here
-    reads the device from the host or changes cache.lens."""
+def block_step(x, conf, shadows, params, cache, layer, S=1):
+    """One block on the S new tokens per sequence: x bf16 [B*S][D] -> x2, row b*S + j at position cache.lens[b] + j; the
+    decode attention also stores the new k, v rows.  No host read-back; cache.lens unchanged.  S == 1, a decode step:
+    BL.linear_fwd_decode and K.attn_decode.  S > 1, a speculative verify step: K.attn_decode_multi, and K.gemm_skinny
+    for every M = B*S <= K.SKINNY_ROWS, whose row bits do not depend on M: a row gets the bits of the S == 1 step."""
     B, _, H, eps = conf[:4]
-    ln1w, ln1b, _, attn_b, _, proj_b, ln2w, ln2b, _, fc_b, _, fc2_b = params
-    wqkv, wproj, wfc, wfc2 = shadows
-    ln1, _, _ = K.layernorm_fwd(x, ln1w, ln1b, eps)
-    qkv = BL.linear_fwd_decode(ln1, wqkv, bias=attn_b)
-    y = K.attn_decode(qkv, cache.k[layer], cache.v[layer], cache.lens, chunk=cache.chunk, part=cache.part,
-                      scale=1.0 / math.sqrt(x.shape[1] // H))
-    x1 = BL.linear_fwd_decode(y, wproj, bias=proj_b, res=x)
-    ln2, _, _ = K.layernorm_fwd(x1, ln2w, ln2b, eps)
-    h = BL.linear_fwd_decode(ln2, wfc, bias=fc_b, act=2)
-    return BL.linear_fwd_decode(h, wfc2, bias=fc2_b, res=x1)
-
-
-def block_verify(x, conf, shadows, params, cache, layer, S):
-    """:func:`block_decode` on the S new tokens per sequence of a speculative step: x bf16 [B*S][D] -> x2, row b*S + j
-    at position cache.lens[b] + j, with attn_decode_multi (which also stores the S new k, v rows) in the middle.  The
-    four linears run on K.gemm_skinny for every M = B*S <= K.SKINNY_ROWS, whose row bits do not depend on M: a row gets
-    the bits block_decode gives it."""
-    B, _, H, eps = conf[:4]
-    ln1w, ln1b, _, attn_b, _, proj_b, ln2w, ln2b, _, fc_b, _, fc2_b = params
-    wqkv, wproj, wfc, wfc2 = shadows
-    if S > cache.S or x.shape[0] != B * S or x.shape[0] > K.SKINNY_ROWS:
-        raise ValueError(f"block_verify: {x.shape[0]} rows for B = {B}, S = {S} (cache S = {cache.S}, at most "
-                         f"{K.SKINNY_ROWS} rows)")
-    ln1, _, _ = K.layernorm_fwd(x, ln1w, ln1b, eps)
-    qkv = K.gemm_skinny(ln1, wqkv, bias=attn_b)
-    y = K.attn_decode_multi(qkv, cache.k[layer], cache.v[layer], cache.lens, S, chunk=cache.chunk, part=cache.part,
-                            scale=1.0 / math.sqrt(x.shape[1] // H))
-    x1 = K.gemm_skinny(y, wproj, bias=proj_b, res=x)
-    ln2, _, _ = K.layernorm_fwd(x1, ln2w, ln2b, eps)
-    h = K.gemm_skinny(ln2, wfc, bias=fc_b, act=2)
-    return K.gemm_skinny(h, wfc2, bias=fc2_b, res=x1)
+    if S == 1:
+        lin, attn, multi = BL.linear_fwd_decode, K.attn_decode, {}
+    else:
+        if S > cache.S or x.shape[0] != B * S or x.shape[0] > K.SKINNY_ROWS:    # (the text of block_verify, now this S > 1)
+            raise ValueError(f"block_verify: {x.shape[0]} rows for B = {B}, S = {S} (cache S = {cache.S}, at most "
+                             f"{K.SKINNY_ROWS} rows)")
+        lin, attn, multi = K.gemm_skinny, K.attn_decode_multi, {"S": S}
+    return _block_infer(x, eps, shadows, params, lin, attn, cache.k[layer], cache.v[layer], cache.lens, chunk=cache.chunk,
+                        part=cache.part, scale=1.0 / math.sqrt(x.shape[1] // H), **multi)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -6,6 +6,8 @@ import copy
 import pytest
 import torch
 
+from pytorch_distributed_nn_amd.generation import fused_stepper
+
 pytestmark = pytest.mark.gpu
 NEW = 40
 
@@ -53,7 +55,7 @@ def test_teacher_forced_logits_against_cpu_fp32(models, P):
     # the cached path, teacher-forced
     with torch.no_grad():
         pl = torch.full((B,), P, dtype=torch.int32, device="cuda")
-        logits, step = gpu._generate_fused(idx.cuda(), pl, NEW, False, None)
+        logits, step = fused_stepper(gpu, idx.cuda(), pl, NEW, False, None)
         got = [logits.clone()]
         for i in range(NEW - 1):
             got.append(step(seq[:, P + i].cuda()).clone())
