@@ -395,7 +395,7 @@ def main(argv=None):
     from . import tuning
     if dev.type == "cuda" and tuning.get("side_wgrad") == 1:
         # as bench.py: the fused ResNets' data-gradient chain runs on a high-priority stream, their weight
-        # gradients on the default-priority side stream (ops/fused_resnet.py), so the dispatcher fills the CUs
+        # gradients on the default-priority side stream (ops/side_stream.py), so the dispatcher fills the CUs
         # with the critical path first
         main_stream = torch.cuda.Stream(device=dev, priority=-1)
         main_stream.wait_stream(torch.cuda.current_stream(dev))

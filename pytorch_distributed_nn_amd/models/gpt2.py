@@ -265,8 +265,8 @@ class GPT2(nn.Module):
         if pf and targets is not None and torch.is_grad_enabled():
             # the data-gradient GEMMs' transposed weight copies, refreshed in one launch at forward start
             # (instead of ~50 small transposes inside the backward)
-            from ..ops.fused_resnet import _side_stream
-            OF.prefetch_weight_t(self._t_weights(), _side_stream(idx.device) if pf == 2 else None)
+            from ..ops.side_stream import side_stream
+            OF.prefetch_weight_t(self._t_weights(), side_stream(idx.device) if pf == 2 else None)
         wte_k, wpe_k = OF.weight_bf16(wte), OF.weight_bf16(wpe)
         # tied wte: with targets the fused LM head and the embedding both accumulate into its arena gradient
         hd = targets is not None and direct_grad(wte) is not None

@@ -20,7 +20,8 @@ import torch.nn.functional as F
 
 from ..ops import functional as OF
 from ..ops import kernels as K
-from ..ops.fused_resnet import BasicBlockFn, BottleneckFn, StemFn, side_forward, stem_shadow
+from ..ops.fused_resnet import BasicBlockFn, BottleneckFn, StemFn, stem_shadow
+from ..ops.side_stream import side_forward, side_stream
 
 
 def _bn_conf(bn: nn.BatchNorm2d):
@@ -156,8 +157,7 @@ class _ResNetBase(nn.Module):
               and b.conv2.out_channels % 128 == 0]
         if not ps:
             return
-        from ..ops.fused_resnet import _side_stream
-        side = _side_stream(x.device)
+        side = side_stream(x.device)
         if side is not None:
             from ..ops.fp8 import prefetch_fp8_weights
             prefetch_fp8_weights(ps, side)

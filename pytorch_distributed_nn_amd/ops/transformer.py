@@ -34,6 +34,7 @@ import torch.nn.functional as F
 from ..optim.flat import direct_grad, grad_ready
 from . import linear as BL
 from . import kernels as K
+from .side_stream import GradSink, side_stream
 from .. import tuning as _tuning
 
 BF16 = torch.bfloat16
@@ -310,49 +311,29 @@ def _wgrad(g, x, shape):
     return dw
 
 
-class _Sink:
+class _Sink(GradSink):
     """Routes parameter gradients straight into the flat arena when possible (optim.flat.direct_grad):
     the GEMM / column-sum / LayerNorm kernels accumulate in place, the op returns None for the parameter
     and announces it with grad_ready.  Otherwise the gradient is returned to autograd.
 
     tuning gpt2_side_wgrad: arena-bound weight gradients run on the ResNets' weight-gradient side stream
-    (ops/fused_resnet.py) beside the data-gradient chain, joined like theirs (at the end of the backward when
-    every hook reading them is side-aware, i.e. DDP's bucket launches)."""
-
-    def __init__(self):
-        self.ready = []
-        self.side = None
-        self.forked = False
-
-    def _tgt(self, p):
-        t = direct_grad(p)
-        if t is not None:
-            self.ready.append(p)
-        return t
-
-    def _side(self, g):
-        if not _tuning.get("gpt2_side_wgrad") or not g.is_cuda:
-            return None
-        from .fused_resnet import _side_stream
-        return _side_stream(g.device)
+    (ops/side_stream.py) beside the data-gradient chain, joined like theirs (GradSink.done)."""
 
     def linear(self, p_w, p_b, g, x):
-        tw = self._tgt(p_w)
-        tb = self._tgt(p_b) if p_b is not None else None
+        tw = self.target(p_w)
+        tb = self.target(p_b) if p_b is not None else None
         bias_in = tb if _tuning.get("bias_in_wgrad") else None
-        side = self._side(g) if tw is not None and (p_b is None or tb is not None) else None
+        side = side_stream(g.device) if (tw is not None and (p_b is None or tb is not None)
+                                         and _tuning.get("gpt2_side_wgrad") and g.is_cuda) else None
         if side is not None:
-            main = torch.cuda.current_stream(g.device)
-            K.stream_wait(side, main)
+            self.side = side
+            self.fork(torch.cuda.current_stream(g.device))
             with torch.cuda.stream(side):
                 bias_done = BL.wgrad_acc(g, x, tw, bias=bias_in, plan_cus=_tuning.get("wgrad_plan_cus"))
                 if p_b is not None and not bias_done:
                     K.colsum(g, out=tb, accumulate=True, deterministic=not _tuning.get("colsum_atomic"))
             for t in (g, x):
                 t.record_stream(side)
-            self.side, self.forked = side, True
-            from .fused_resnet import _FORKS
-            _FORKS[g.device.index] = _FORKS.get(g.device.index, 0) + 1
             return None, None
         bias_done = False
         if tw is not None:
@@ -370,23 +351,11 @@ class _Sink:
         return rw, rb
 
     def layernorm(self, dy, x, w, m, r, dres, p_w, p_b):
-        tw, tb = direct_grad(p_w), direct_grad(p_b)
-        if tw is not None and tb is not None:
-            self.ready += [p_w, p_b]
-            dx, _, _ = K.layernorm_bwd(dy, x, w, m, r, dres=dres, acc=(tw, tb))
+        acc = self.acc(p_w, p_b)
+        if acc is not None:
+            dx, _, _ = K.layernorm_bwd(dy, x, w, m, r, dres=dres, acc=tuple(acc))
             return dx, None, None
         return K.layernorm_bwd(dy, x, w, m, r, dres=dres)
-
-    def done(self):
-        if self.forked:
-            self.forked = False
-            from .fused_resnet import _join_at_backward_end
-            if all(getattr(fn, "_pdnn_side_aware", False) for p in self.ready for fn in getattr(p, "_pdnn_grad_hooks", ())):
-                _join_at_backward_end(self.side)
-            else:
-                K.stream_wait(torch.cuda.current_stream(self.side.device), self.side)
-        for p in self.ready:
-            grad_ready(p)
 
 
 class BlockConf(NamedTuple):

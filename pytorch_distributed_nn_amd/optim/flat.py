@@ -26,7 +26,7 @@ ALIGN = 64
 # bumped by every bf16-shadow re-cast issued while a forward may be running (a PS weight bucket landing, an
 # on-the-fly re-cast of an externally modified weight): those casts run on the compute stream mid-forward,
 # so a side stream that forked from the compute stream earlier in the forward must fork again before it
-# reads the shadow (ops/fused_resnet._prep_dgrad_weights)
+# reads the shadow (ops/side_stream.prep_weights)
 SHADOW_EPOCH = [0]
 
 

@@ -63,7 +63,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from ..ops.fused_resnet import side_stream_if_active
+from ..ops.side_stream import side_stream_if_active
 from ..optim.flat import ParamUseMode, flatten_module, register_grad_ready_hook, reverse_buckets
 
 
@@ -461,7 +461,7 @@ class DistributedDataParallel(nn.Module):
 
     def _launch(self, b, zero=False):
         # Fused ResNet blocks write weight gradients on a side stream and do not join it back before announcing
-        # them (ops/fused_resnet.py): the bucket's collective (and any zero-fill / cast of the bucket) is issued
+        # them (ops/side_stream.py): the bucket's collective (and any zero-fill / cast of the bucket) is issued
         # from the side stream after it has caught up with the compute stream, so it is ordered after both
         # while the compute stream runs on into the next block's backward.
         if self.kofn is not None and self.throttle and self.flat.grad.is_cuda:

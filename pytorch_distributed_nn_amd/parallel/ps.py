@@ -68,7 +68,7 @@ from dataclasses import dataclass, field
 import torch
 import torch.distributed as dist
 
-from ..ops.fused_resnet import side_stream_if_active
+from ..ops.side_stream import side_stream_if_active
 from ..optim.flat import ParamUseMode, flatten_module, register_grad_ready_hook, reverse_buckets
 from ..utils.native import PSCoordinator, Store, StoreServer, StoreTimeout
 
