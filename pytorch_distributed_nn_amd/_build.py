@@ -46,6 +46,7 @@ HIP_FLAGS = [
 # tiles held AGPRs; VGPR form there measured +1.9% on the ResNet-50 step (7142/7199 -> 7312/7293 img/s).
 VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 KERNEL_FILE_FLAGS = {"attention.hip": VGPR_FORM, "gemm_mfma.hip": VGPR_FORM, "gemm_pp.hip": VGPR_FORM}   # gemm: +1.9% ResNet-50
+KERNEL_FILE_FLAGS["attention_extend.hip"] = VGPR_FORM       # attention.hip's forward at an offset: the same mix
 CXX_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-Wno-unused-parameter",
              "-pthread", f"-I{ROOT / 'csrc' / 'include'}", f"-I{ROOT / 'csrc' / 'runtime'}"]
 

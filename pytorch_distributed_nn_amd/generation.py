@@ -1,6 +1,8 @@
 """GPT-2 generation behind ``GPT2.generate`` (its docstring is the contract): one check of the arguments, one GPU
 :class:`Engine` (``rows`` is the one copy of the decode forward), its CPU :class:`Reference`, one :class:`Replay` helper,
-and per sampler a short unit around ``Engine.rows`` with its driver.  Kernels are called as ``K.name`` / ``BL.name``."""
+and per sampler a short unit around ``Engine.rows`` with its driver.  ``resume=True`` ingests through ``Engine.extend``
+behind a kept cache instead of ``prefill``; :class:`Session` keeps the accounting of a conversation over several such
+calls.  Kernels are called as ``K.name`` / ``BL.name``."""
 from __future__ import annotations
 
 from collections import namedtuple
@@ -36,11 +38,12 @@ def sample(logits, temperature, top_k, generator, top_p=None):
 
 # one checked call: N = max_new_tokens, pl = the B prompt lengths, draw = dict(temperature, top_k, top_p), seed masked to
 # 63 bits (sampler="device", else None), S = speculate or None, guess = the draft table or None (n-gram drafts)
-Request = namedtuple("Request", "B P N pl draw eos generator seed S guess ngram graph return_logits return_stats cache")
+Request = namedtuple("Request", "B P N pl draw eos generator seed S guess ngram graph return_logits return_stats cache "
+                     "resume", defaults=(False,))
 
 
 def check_args(c, idx, max_new_tokens, *, temperature, top_k, eos_token, prompt_lens, generator, graph,
-               return_logits, cache, top_p, sampler, seed, speculate, draft, ngram, return_stats):
+               return_logits, cache, top_p, sampler, seed, speculate, draft, ngram, return_stats, resume=False):
     """``generate``'s arguments and the model's config ``c`` -> :class:`Request`, or the first refusal in this order"""
     if idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
         raise ValueError(f"generate: idx must be [B][P] with B, P >= 1, got {tuple(idx.shape)}")
@@ -92,9 +95,30 @@ def check_args(c, idx, max_new_tokens, *, temperature, top_k, eos_token, prompt_
         raise ValueError("generate: return_stats needs speculate")
     if idx.is_cuda:
         TX.need_fused_kernels(c.n_embd, c.n_head)
+    if resume:
+        check_resume(c, idx, B, pl, max_new_tokens, S, cache)
     return Request(B, P, max_new_tokens, pl, dict(temperature=float(temperature), top_k=top_k, top_p=top_p), eos_token,
                    generator, int(seed) & ((1 << 63) - 1) if sampler == "device" else None, S, guess, ngram, graph,
-                   return_logits, return_stats, cache)
+                   return_logits, return_stats, cache, bool(resume))
+
+
+def check_resume(c, idx, B, pl, N, S, cache):
+    """The refusals of ``resume=True``, after every other one.  The last reads cache.lens to the host, the call's one
+    read-back before its first launch: every row must fit lens[b] + prompt_lens[b] + max_new_tokens (+ S)."""
+    if cache is None or getattr(cache, "B", None) != B:
+        raise ValueError(f"generate: resume=True continues a kept cache: pass cache=, an ops.transformer.KVCache of B = "
+                         f"{B}, got {'none' if cache is None else f'one of B = {cache.B}'}")
+    if not idx.is_cuda:
+        raise ValueError("generate: resume=True runs on the GPU only (the CPU path keeps no cache between calls); "
+                         "generation.Session (GPT2.session) holds a conversation on either device")
+    if cache.k.device != idx.device or (S or 1) > cache.S:
+        raise ValueError(f"generate: resume=True with a cache of S = {cache.S} on {cache.k.device}, need S >= {S or 1} on "
+                         f"{idx.device}")
+    room, extra = min(c.block_size, cache.Tmax), N + (S or 0)
+    for b, (have, new) in enumerate(zip(cache.lens.tolist(), pl)):
+        if have < 0 or have + new + extra > room:
+            raise ValueError(f"generate: resume=True, row {b}: {have} cached + {new} new + {extra} to generate > "
+                             f"{room} = min(block size, cache Tmax)")
 
 
 class Replay:
@@ -118,16 +142,19 @@ class Replay:
 class Engine:
     """One call's GPU model: the cache (``cache`` if it fits, reset; else a new one), bf16 shadows, block parameters"""
 
-    def __init__(self, model, B, P, N, S=1, cache=None):
+    def __init__(self, model, B, P, N, S=1, cache=None, resume=False):
         self.config, tr = model.config, model.transformer
         dev = tr.wte.weight.device
         Tneed = model.kv_cache_len(P, N + (S if S > 1 else 0))       # rejected drafts occupy slots past the accepted length
-        if cache is None:
+        if resume:                                      # check_resume has held the kept cache against this call
+            pass
+        elif cache is None:
             cache = TX.KVCache(model, B, Tneed, dev, S=S)
         elif cache.B != B or cache.Tmax < Tneed or cache.k.device != dev or cache.S < S:
             raise ValueError(f"generate: cache of B = {cache.B}, Tmax = {cache.Tmax}, S = {cache.S} on {cache.k.device} does "
                              f"not fit B = {B}, Tmax >= {Tneed}, S >= {S} on {dev}")
-        cache.reset()
+        if not resume:
+            cache.reset()
         self.B, self.cache = B, cache
         self.wte_k, self.wpe_k = OF.weight_bf16(tr.wte.weight), OF.weight_bf16(tr.wpe.weight)
         self.blocks = [blk.fused_params() for blk in tr.h]
@@ -149,6 +176,26 @@ class Engine:
         logits = BL.linear_fwd_decode(xf, self.wte_k)
         cache.lens.copy_(pl_dev)
         return logits
+
+    def extend(self, idx, pl_dev):
+        """Resume: idx int64 [B][P] are the tokens behind the cache.lens[b] cached ones (row b: its first pl_dev[b]), run
+        as Tq = P rounded up to K.EXTEND_TILE rows per sequence at positions lens[b] + j -> bf16 logits [B][V] at each
+        row's last token; cache.lens += pl_dev.  The padding rows' keys land past the new lens, where anything may be."""
+        c, cache = self.config, self.cache
+        B, P = idx.shape
+        Tq = -(-P // K.EXTEND_TILE) * K.EXTEND_TILE
+        pos = (cache.lens[:, None] + torch.arange(Tq, device=idx.device, dtype=torch.int32)[None, :]).reshape(-1)
+        x = K.embedding_decode(F.pad(idx, (0, Tq - P)).reshape(-1).contiguous(), pos.contiguous(), self.wte_k, self.wpe_k)
+        for layer, (params, shadows) in enumerate(self.blocks):
+            x = TX.block_extend(x, (B, Tq, c.n_head, c.eps), shadows, params, cache, layer)
+        last = torch.arange(B, device=idx.device) * Tq + pl_dev.long() - 1
+        xf, _, _ = K.layernorm_fwd(x.index_select(0, last), self.lnw, self.lnb, c.eps)
+        logits = BL.linear_fwd_decode(xf, self.wte_k)
+        cache.lens.add_(pl_dev)
+        return logits
+
+    def ingest(self, idx, pl_dev, resume):
+        return self.extend(idx, pl_dev) if resume else self.prefill(idx, pl_dev)
 
     def rows(self, tok, pos, S=1):
         """Row b*S + j: token tok[b*S + j] at position pos[b*S + j] (clamped to the table) and cache slot cache.lens[b] + j
@@ -202,12 +249,12 @@ class Reference:
         return self.model.lm_head(tr.ln_f(x)).float()
 
 
-def fused_stepper(model, idx, pl_dev, max_new_tokens, graph=False, cache=None):
+def fused_stepper(model, idx, pl_dev, max_new_tokens, graph=False, cache=None, resume=False):
     """GPU: prefill -> (fp32 logits [B][V] at each prompt's last position, step(tok) -> the next logits, in one fp32
     buffer).  The engine of the torch-sampler loop: the token comes from the host side of the loop."""
     B, P = idx.shape
-    eng = Engine(model, B, P, max_new_tokens, 1, cache)
-    logits16 = eng.prefill(idx, pl_dev)
+    eng = Engine(model, B, P, max_new_tokens, 1, cache, resume)
+    logits16 = eng.ingest(idx, pl_dev, resume)
     tok_buf = torch.zeros(B, dtype=torch.int64, device=idx.device)
     logits = logits16.float()
     logit_buf = torch.empty_like(logits)
@@ -316,6 +363,9 @@ def generate(model, idx, max_new_tokens, **kw):
     B, P, N = r.B, r.P, r.N
     idx = idx.long()
     out = torch.cat([idx, idx.new_zeros(B, N)], 1)
+    if N == 0 and r.resume:                             # chunked prefill: the ingest is the whole call
+        Engine(model, B, P, 0, r.S or 1, r.cache, True).extend(idx, torch.tensor(r.pl, device=idx.device,
+                                                                                 dtype=torch.int32))
     if N == 0:
         if r.return_stats:
             return out, {"verify_steps": 0, "stats": [0] * (r.S + 1)}
@@ -324,8 +374,8 @@ def generate(model, idx, max_new_tokens, **kw):
     if r.guess is not None:
         r = r._replace(guess=r.guess.to(idx.device).contiguous())
     if r.seed is not None and idx.is_cuda:         # the sampling kernel is inside the step: the loop is on the device
-        eng = Engine(model, B, P, N, r.S or 1, r.cache)
-        logit_buf = eng.prefill(idx, pl_dev)
+        eng = Engine(model, B, P, N, r.S or 1, r.cache, r.resume)
+        logit_buf = eng.ingest(idx, pl_dev, r.resume)
         res = _speculate_device(eng, r, pl_dev, out, logit_buf) if r.S else _device_loop(eng, r, out, logit_buf)
         return (out, res) if r.return_logits or r.return_stats else out
     if r.S:
@@ -333,7 +383,7 @@ def generate(model, idx, max_new_tokens, **kw):
         return (out, stats) if r.return_stats else out
     # the token is drawn on the host side of the loop: the torch sampler on both devices, the device sampler's reference
     if idx.is_cuda:
-        logits, step = fused_stepper(model, idx, pl_dev, N, r.graph, r.cache)
+        logits, step = fused_stepper(model, idx, pl_dev, N, r.graph, r.cache, r.resume)
     else:
         ref = Reference(model, B, max(r.pl) + N)
         logits, step = ref.prefill(idx, pl_dev), ref.step
@@ -355,3 +405,72 @@ def generate(model, idx, max_new_tokens, **kw):
         if i + 1 < N:
             logits = step(tok)
     return (out, torch.stack(kept, 1)) if r.return_logits else out
+
+
+class Session:
+    """A conversation of B rows over several ``generate`` calls that keeps the key/value cache between them
+    (``GPT2.session``).  Host-side accounting only: ``history[b]`` is every token of row b so far (the turns and the
+    emitted tokens, cut after the first ``eos_token`` of each call) and ``cached[b]`` how many of them are in the cache.
+
+    Invariant: slot i of row b of the cache holds the K/V of history[b][i] for every i < cached[b].
+
+    :meth:`generate` packs, for each row, the uncached tail of the history (the last token a call emits is never run
+    through the model, so it is cached by the next call) followed by the new turn, and runs ``generate(resume=True)`` on
+    it: a turn costs its own tokens against the cache, not the whole history again.  On the CPU there is no cache: the
+    same call re-runs ``generate`` on the concatenated history, which is the definition the GPU path is held to."""
+
+    def __init__(self, model, B, max_len, S=1):
+        if B < 1 or not 1 <= max_len <= model.config.block_size:
+            raise ValueError(f"session: B >= 1 and 1 <= max_len <= block size {model.config.block_size}, got B = {B}, "
+                             f"max_len = {max_len}")
+        self.model, self.B, self.max_len = model, B, max_len
+        self.device = model.transformer.wte.weight.device
+        self.history, self.cached = [[] for _ in range(B)], [0] * B
+        self.cache = TX.KVCache(model, B, max_len, self.device, S=S) if self.device.type == "cuda" else None
+
+    def generate(self, turns, max_new_tokens, *, eos_token=None, **sampling):
+        """``turns``: B token sequences (lists or 1-D tensors), row b's next turn; it may be empty only where the row has
+        an uncached tail.  ``sampling``: generate's temperature, top_k, top_p, sampler, seed, speculate, draft, ngram,
+        generator, graph.  -> the new tokens per row, B lists, each cut after its first ``eos_token``."""
+        if len(turns) != self.B:
+            raise ValueError(f"session: {self.B} turns expected, got {len(turns)}")
+        for bad in ("cache", "resume", "prompt_lens", "return_logits", "return_stats"):
+            if bad in sampling:
+                raise ValueError(f"session: {bad} is the session's own argument of generate")
+        N = int(max_new_tokens)
+        hist = [h + [int(t) for t in (turn.tolist() if torch.is_tensor(turn) else turn)]
+                for h, turn in zip(self.history, turns)]
+        gpu = self.cache is not None
+        rows = [h[n:] for h, n in zip(hist, self.cached)] if gpu else hist
+        pl = [len(r) for r in rows]
+        if min(pl) < 1 or max(len(h) for h in hist) + N > self.max_len:
+            raise ValueError(f"session: every row needs a token to run and history + max_new_tokens <= max_len = "
+                             f"{self.max_len}; got {pl} tokens to run, histories of {[len(h) for h in hist]}")
+        P = max(pl)
+        idx = torch.tensor([r + [0] * (P - len(r)) for r in rows], dtype=torch.int64, device=self.device)
+        if gpu:
+            out = self.model.generate(idx, N, eos_token=eos_token, prompt_lens=pl, cache=self.cache, resume=True,
+                                      **sampling)
+        elif N:
+            out = self.model.generate(idx, N, eos_token=eos_token, prompt_lens=pl, **sampling)
+        else:
+            out = idx
+        new = [row[P:P + N] for row in out.tolist()]
+        if eos_token is not None:
+            new = [n[:n.index(int(eos_token)) + 1] if int(eos_token) in n else n for n in new]
+        if gpu:     # slots behind the ingested tokens hold the emitted tokens that were run, in order: keep the cut ones
+            base = [len(h) for h in hist]
+            self.cached = [b0 + max(0, min(len(n), have - b0)) for b0, n, have in zip(base, new, self.cache.lens.tolist())]
+            self.cache.truncate(self.cached)
+        self.history = [h + n for h, n in zip(hist, new)]
+        return new
+
+    def truncate(self, lens):
+        """Rewind every row to its first lens[b] tokens (an int: all rows): history and cache.  The last kept token is
+        left to the next call to run, as after a call that emitted it: a turn repeated behind the rewound history is
+        then the computation it was the first time, and its tokens repeat bitwise."""
+        lens = [int(lens)] * self.B if not hasattr(lens, "__len__") else [int(v) for v in lens]
+        self.history = [h[:max(n, 0)] for h, n in zip(self.history, lens)]
+        self.cached = [min(c, max(len(h) - 1, 0)) for c, h in zip(self.cached, self.history)]
+        if self.cache is not None:
+            self.cache.truncate(self.cached)

@@ -303,7 +303,7 @@ class GPT2(nn.Module):
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, *, temperature=1.0, top_k=None, eos_token=None, prompt_lens=None,
                  generator=None, graph=False, return_logits=False, cache=None, top_p=None, sampler="torch", seed=None,
-                 speculate=None, draft="ngram", ngram=3, return_stats=False):
+                 speculate=None, draft="ngram", ngram=3, return_stats=False, resume=False):
         """Sample ``max_new_tokens`` tokens after the prompts ``idx`` int [B][P] with a key/value cache: one prefill over
         the prompt, then one single-token step per new token (GPU: ``ops.transformer.block_step`` on the decode
         attention kernel of ``csrc/kernels/attention_decode.hip``; CPU: plain PyTorch in fp32 with per-layer k, v lists,
@@ -345,11 +345,25 @@ class GPT2(nn.Module):
         units.  The GPU path needs tuning ``decode_skinny``, B <= 8 and B * S <= 64; a passed ``cache`` needs ``S`` >= S
         and Tmax >= kv_cache_len(P, max_new_tokens + S) (rejected drafts occupy slots past the accepted length).
         ``return_logits`` is not available with ``speculate``.  ``return_stats=True`` appends a dict: ``verify_steps``
-        and ``stats``, where stats[e] counts the (row, verify step) pairs of incomplete rows that emitted e tokens."""
+        and ``stats``, where stats[e] counts the (row, verify step) pairs of incomplete rows that emitted e tokens.
+
+        ``resume=True`` (GPU, needs ``cache``): the cache is kept, not reset.  idx[b, :prompt_lens[b]] are the tokens that
+        follow the cache.lens[b] cached ones; they are ingested by ``Engine.extend`` (``ops.transformer.block_extend`` on
+        the append + extend kernels of ``csrc/kernels/attention_extend.hip``: many queries at an offset against the
+        cache) instead of the prefill, and every sampler loop above runs unchanged on top.  ``max_new_tokens == 0`` still
+        ingests, so a long prompt can be fed in chunks.  cache.lens is read to the host once, before the first launch:
+        every row needs lens[b] + prompt_lens[b] + max_new_tokens (+ S) <= min(block size, cache.Tmax).  Afterwards
+        cache.lens counts the tokens that were run (the last emitted token is not among them); :meth:`session` keeps
+        that account over several turns."""
         return G.generate(self, idx, max_new_tokens, temperature=temperature, top_k=top_k, eos_token=eos_token,
                           prompt_lens=prompt_lens, generator=generator, graph=graph, return_logits=return_logits,
                           cache=cache, top_p=top_p, sampler=sampler, seed=seed, speculate=speculate, draft=draft,
-                          ngram=ngram, return_stats=return_stats)
+                          ngram=ngram, return_stats=return_stats, resume=resume)
+
+    def session(self, B, max_len, S=1):
+        """A :class:`generation.Session`: B conversations of up to ``max_len`` tokens whose key/value cache is kept from
+        one ``session.generate(turns, max_new_tokens, ...)`` to the next (``S``: the largest ``speculate`` to be used)"""
+        return G.Session(self, B, max_len, S)
 
     def _forward_reference(self, idx, targets=None, doc=None, drop=None):
         B, T = idx.shape

@@ -151,6 +151,9 @@ _SIGS = {
     "pdnn_spec_prepare": [P, I, I, I, P, P, P, ctypes.c_longlong, P, I, I, I, P, P, P, P],
     "pdnn_spec_accept": [P, P, P, I, I, I, P, P, P, ctypes.c_longlong, P, P, I, I, P],
     "pdnn_kv_cache_fill": [P, P, P, I, I, I, I, P],
+    "pdnn_kv_cache_append": [P, P, P, P, I, I, I, I, P],
+    "pdnn_attn_extend": [P, P, P, P, P, I, I, I, I, F, P],
+    "pdnn_attn_extend_tile": [],
     "pdnn_dropout_add_fwd": [P, P, P, L, I, F, P, I, P],
     "pdnn_dropout_bwd": [P, P, L, I, F, P, I, P],
     "pdnn_dropout_mask_rows": [P, L, I, F, P, I, P],

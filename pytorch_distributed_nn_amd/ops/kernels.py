@@ -1660,6 +1660,46 @@ def kv_cache_fill(qkv, kcache, vcache, B, T):
     call("pdnn_kv_cache_fill", ptr(qkv), ptr(kcache), ptr(vcache), B, T, H, Tmax, stream())
 
 
+# ----------------------------------------------------------------------------------- extend attention (attention_extend.hip)
+EXTEND_TILE = 64            # queries per block of attn_extend (pdnn_attn_extend_tile): Tq must be a multiple of it
+
+
+def _extend_chk(name, qkv, kcache, vcache, lens):
+    """-> (B, Tq, H, Tmax) of one kv_cache_append / attn_extend call"""
+    _bf16_c(qkv, f"{name}.qkv")
+    _cache_chk(name, kcache, vcache, qkv.device)
+    B, H, Tmax, _ = kcache.shape
+    _chk(qkv.dim() == 2 and qkv.shape[1] == 3 * H * 64 and qkv.shape[0] >= B and qkv.shape[0] % (B * EXTEND_TILE) == 0,
+         f"{name}: qkv {tuple(qkv.shape)} for B={B} H={H}: expected [B*Tq][3*H*64] with Tq a multiple of {EXTEND_TILE}")
+    _chk(torch.is_tensor(lens) and lens.dtype == torch.int32 and lens.shape == (B,) and lens.is_contiguous()
+         and lens.device == qkv.device, f"{name}: lens must be contiguous int32 [{B}] on {qkv.device}")
+    _chk(lib().pdnn_attn_extend_tile() == EXTEND_TILE, f"{name}: the library's tile is not EXTEND_TILE = {EXTEND_TILE}")
+    return B, qkv.shape[0] // B, H, Tmax
+
+
+def kv_cache_append(qkv, kcache, vcache, lens):
+    """The K and V columns of qkv bf16 [B*Tq][3*H*64] behind the cached tokens: row b*Tq + j into slot lens[b] + j of
+    kcache / vcache bf16 [B][H][Tmax][64] (a slot >= Tmax is not stored).  lens int32 [B] on the device is read by the
+    kernel only and not changed.  Tq % EXTEND_TILE == 0."""
+    B, Tq, H, Tmax = _extend_chk("kv_cache_append", qkv, kcache, vcache, lens)
+    call("pdnn_kv_cache_append", ptr(qkv), ptr(kcache), ptr(vcache), ptr(lens), B, Tq, H, Tmax, stream())
+
+
+def attn_extend(qkv, kcache, vcache, lens, out=None, scale=None):
+    """Tq new tokens per sequence against the cache, after :func:`kv_cache_append` of the same qkv on the same stream:
+    query row b*Tq + j sits at position lens[b] + j and sees the cache keys 0 .. lens[b] + j (every key is read from the
+    cache).  -> out bf16 [B*Tq][H*64].  ``lens`` is not changed; ``scale`` defaults to 1 / 8."""
+    B, Tq, H, Tmax = _extend_chk("attn_extend", qkv, kcache, vcache, lens)
+    if out is None:
+        out = torch.empty(B * Tq, H * 64, device=qkv.device, dtype=BF16)
+    else:
+        _chk(out.dtype == BF16 and out.shape == (B * Tq, H * 64) and out.is_contiguous() and out.device == qkv.device,
+             f"attn_extend: out must be contiguous bf16 [{B * Tq}][{H * 64}] on {qkv.device}")
+    call("pdnn_attn_extend", ptr(qkv), ptr(kcache), ptr(vcache), ptr(lens), ptr(out), B, Tq, H, Tmax,
+         float(0.125 if scale is None else scale), stream())
+    return out
+
+
 # ----------------------------------------------------------------------------------- dropout (csrc/kernels/dropout_rng.h)
 def dropout_p_eff(p):
     """The probability the kernels use for ``p``: quantised to thr / 256 (the scale is 1 / (1 - p_eff))."""

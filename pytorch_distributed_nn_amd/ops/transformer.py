@@ -507,6 +507,12 @@ class KVCache:
     def reset(self):
         self.lens.zero_()
 
+    def truncate(self, lens):
+        """Rewind: lens[b] = min(lens[b], ``lens``[b]) on the device (``lens``: an int, or B of them).  Slots past lens
+        may hold anything, so rewinding is only that."""
+        self.lens.copy_(torch.minimum(self.lens, torch.as_tensor(lens, device=self.lens.device).to(torch.int32)
+                                      .expand_as(self.lens)))
+
 
 def need_fused_kernels(D, H, T=None):
     """Generation runs on the head-dim-64 kernels only, a prefill (``T`` given) on the flash kernels (:func:`use_flash`)"""
@@ -560,6 +566,23 @@ def block_step(x, conf, shadows, params, cache, layer, S=1):
         lin, attn, multi = K.gemm_skinny, K.attn_decode_multi, {"S": S}
     return _block_infer(x, eps, shadows, params, lin, attn, cache.k[layer], cache.v[layer], cache.lens, chunk=cache.chunk,
                         part=cache.part, scale=1.0 / math.sqrt(x.shape[1] // H), **multi)
+
+
+def block_extend(x, conf, shadows, params, cache, layer):
+    """One block on Tq new tokens per sequence behind a non-empty cache: x bf16 [B*Tq][D], conf = (B, Tq, H, eps), Tq a
+    multiple of K.EXTEND_TILE -> x2, row b*Tq + j at position cache.lens[b] + j.  The attention appends the new k, v rows
+    to ``cache`` layer ``layer`` and then runs K.attn_extend over the cache; the linears are BL.linear_fwd.  No host
+    read-back; cache.lens unchanged."""
+    B, Tq, H, eps = conf[:4]
+    need_fused_kernels(x.shape[1], H)
+    if Tq % K.EXTEND_TILE or x.shape[0] != B * Tq or cache.B != B:
+        raise ValueError(f"block_extend: {x.shape[0]} rows for B = {B}, Tq = {Tq} (a multiple of {K.EXTEND_TILE}), cache "
+                         f"B = {cache.B}")
+
+    def attn(qkv):
+        K.kv_cache_append(qkv, cache.k[layer], cache.v[layer], cache.lens)
+        return K.attn_extend(qkv, cache.k[layer], cache.v[layer], cache.lens, scale=1.0 / math.sqrt(x.shape[1] // H))
+    return _block_infer(x, eps, shadows, params, BL.linear_fwd, attn)
 
 
 # ------------------------------------------------------------------------------------------------

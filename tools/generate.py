@@ -5,6 +5,7 @@ random initialisation, with GPT2.generate (key/value cache; on a GPU the decode-
     python tools/generate.py --network gpt2_small --checkpoint ckpt.pt --prompt-ids 1,2,3 --max-new-tokens 32
     python tools/generate.py --network gpt2_tiny --random-init --prompt-ids prompt.npy --top-k 40 --seed 1
     python tools/generate.py --network gpt2_small --random-init --prompt-ids 1,2,3,1,2,3 --sampler device --speculate 4
+    python tools/generate.py --network gpt2_small --random-init --prompt-ids prompt.npy --chunk 256
 
 The prompt is a list of token ids (``1,2,3``) or a .npy file holding an integer vector [P] or matrix [B][P]; there is no
 tokenizer here.  Prints one line of comma-separated ids per row: the prompt followed by the new tokens."""
@@ -56,6 +57,9 @@ def build_parser():
                     help="speculative decoding: verify S tokens per step (2..8, needs --sampler device); the tokens are "
                          "those of the plain loop, and the acceptance statistics go to stderr")
     ap.add_argument("--draft-ngram", type=int, default=3, metavar="n", help="longest n-gram of the prompt-lookup draft")
+    ap.add_argument("--chunk", type=int, default=None, metavar="C",
+                    help="ingest the prompt in pieces of C tokens through generate(resume=True) on a kept cache before "
+                         "sampling (GPU; the CPU path keeps no cache and runs the prompt in one piece)")
     return ap
 
 
@@ -85,9 +89,26 @@ def main(argv=None):
         draw = dict(generator=torch.Generator(device=dev).manual_seed(args.seed))
     if args.speculate is not None:
         draw.update(speculate=args.speculate, ngram=args.draft_ngram, return_stats=True)
+    if args.chunk is not None and args.chunk < 1:
+        raise SystemExit(f"--chunk {args.chunk}: expected a positive number of tokens")
+    kw = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, eos_token=args.eos_token,
+              graph=args.graph and dev.type == "cuda", **draw)
+    idx = idx.to(dev)
     try:
-        out = model.generate(idx.to(dev), args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
-                             top_p=args.top_p, eos_token=args.eos_token, graph=args.graph and dev.type == "cuda", **draw)
+        if args.chunk is not None and dev.type == "cuda":
+            from pytorch_distributed_nn_amd.ops.transformer import KVCache
+            S = args.speculate or 1
+            cache = KVCache(model, idx.shape[0], idx.shape[1] + args.max_new_tokens + (S if S > 1 else 0), dev, S=S)
+            pieces = list(idx.split(args.chunk, dim=1))
+            for piece in pieces[:-1]:
+                model.generate(piece, 0, cache=cache, resume=True)
+            out = model.generate(pieces[-1], args.max_new_tokens, cache=cache, resume=True, **kw)
+            head = idx[:, :idx.shape[1] - pieces[-1].shape[1]]
+            out = (torch.cat([head, out[0]], 1), out[1]) if args.speculate is not None else torch.cat([head, out], 1)
+        else:
+            if args.chunk is not None:
+                print("--chunk: no cache is kept on the CPU, the prompt runs in one piece", file=sys.stderr)
+            out = model.generate(idx, args.max_new_tokens, **kw)
     except ValueError as e:
         raise SystemExit(str(e))
     if args.speculate is not None:
