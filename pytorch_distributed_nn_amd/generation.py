@@ -15,6 +15,7 @@ from .ops import functional as OF
 from .ops import kernels as K
 from .ops import linear as BL
 from .ops import transformer as TX
+from .ops.quant import dequantize_rows, quantize_rows_reference
 from .ops.sampling import sample_reference
 from .ops.speculate import accept_reference, prepare_reference
 
@@ -39,11 +40,36 @@ def sample(logits, temperature, top_k, generator, top_p=None):
 # one checked call: N = max_new_tokens, pl = the B prompt lengths, draw = dict(temperature, top_k, top_p), seed masked to
 # 63 bits (sampler="device", else None), S = speculate or None, guess = the draft table or None (n-gram drafts)
 Request = namedtuple("Request", "B P N pl draw eos generator seed S guess ngram graph return_logits return_stats cache "
-                     "resume", defaults=(False,))
+                     "resume decode_weights", defaults=(False, "bf16"))
+
+
+class DecodeWeights:
+    """The fp8 decode weights of a model (``decode_weights="fp8"``): the four linears of every block and the tied LM
+    head as pairs (q e4m3fn codes, inv fp32 row scales) in the format of ops/quant.py, quantised from the bf16 weights
+    when this is made (GPU: K.quant_rows_e4m3; CPU: quantize_rows_reference).  A snapshot: later updates of the model's
+    weights do not reach it."""
+
+    def __init__(self, model):
+        tr = model.transformer
+        if tr.wte.weight.is_cuda:
+            quant = lambda w: K.quant_rows_e4m3(OF.weight_bf16(w))                          # noqa: E731
+        else:
+            quant = lambda w: quantize_rows_reference(w.detach().to(torch.bfloat16))         # noqa: E731
+        self.blocks = [tuple(quant(w) for w in (blk.attn.c_attn.weight, blk.attn.c_proj.weight, blk.mlp.c_fc.weight,
+                                                blk.mlp.c_proj.weight)) for blk in tr.h]
+        self.wte = quant(tr.wte.weight)
+
+    @staticmethod
+    def of(model, decode_weights):
+        """generate's argument -> None ("bf16"), a new snapshot ("fp8") or the given one"""
+        if isinstance(decode_weights, DecodeWeights):
+            return decode_weights
+        return DecodeWeights(model) if decode_weights == "fp8" else None
 
 
 def check_args(c, idx, max_new_tokens, *, temperature, top_k, eos_token, prompt_lens, generator, graph,
-               return_logits, cache, top_p, sampler, seed, speculate, draft, ngram, return_stats, resume=False):
+               return_logits, cache, top_p, sampler, seed, speculate, draft, ngram, return_stats, resume=False,
+               decode_weights="bf16"):
     """``generate``'s arguments and the model's config ``c`` -> :class:`Request`, or the first refusal in this order"""
     if idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
         raise ValueError(f"generate: idx must be [B][P] with B, P >= 1, got {tuple(idx.shape)}")
@@ -97,9 +123,16 @@ def check_args(c, idx, max_new_tokens, *, temperature, top_k, eos_token, prompt_
         TX.need_fused_kernels(c.n_embd, c.n_head)
     if resume:
         check_resume(c, idx, B, pl, max_new_tokens, S, cache)
+    if not (isinstance(decode_weights, DecodeWeights) or decode_weights in ("bf16", "fp8")):
+        raise ValueError(f"generate: decode_weights must be 'bf16' or 'fp8', got {decode_weights!r}")
+    if decode_weights != "bf16" and idx.is_cuda and (not tuning.get("decode_skinny") or B * (S or 1) > K.SKINNY_ROWS
+                                                      or c.n_embd % 16):
+        raise ValueError(f"generate: decode_weights='fp8' on the GPU needs tuning decode_skinny on, B * speculate <= "
+                         f"{K.SKINNY_ROWS} (the fp8 weights have the skinny kernel only) and n_embd % 16 == 0; got "
+                         f"decode_skinny = {tuning.get('decode_skinny')!r}, B = {B}, S = {S}, n_embd = {c.n_embd}")
     return Request(B, P, max_new_tokens, pl, dict(temperature=float(temperature), top_k=top_k, top_p=top_p), eos_token,
                    generator, int(seed) & ((1 << 63) - 1) if sampler == "device" else None, S, guess, ngram, graph,
-                   return_logits, return_stats, cache, bool(resume))
+                   return_logits, return_stats, cache, bool(resume), decode_weights)
 
 
 def check_resume(c, idx, B, pl, N, S, cache):
@@ -140,9 +173,11 @@ class Replay:
 
 
 class Engine:
-    """One call's GPU model: the cache (``cache`` if it fits, reset; else a new one), bf16 shadows, block parameters"""
+    """One call's GPU model: the cache (``cache`` if it fits, reset; else a new one), bf16 shadows, block parameters.
+    ``dec`` (a :class:`DecodeWeights`): ``rows`` and every LM-head GEMM run on its fp8 pairs; prefill and extend blocks
+    keep the bf16 shadows."""
 
-    def __init__(self, model, B, P, N, S=1, cache=None, resume=False):
+    def __init__(self, model, B, P, N, S=1, cache=None, resume=False, dec=None):
         self.config, tr = model.config, model.transformer
         dev = tr.wte.weight.device
         Tneed = model.kv_cache_len(P, N + (S if S > 1 else 0))       # rejected drafts occupy slots past the accepted length
@@ -159,6 +194,9 @@ class Engine:
         self.wte_k, self.wpe_k = OF.weight_bf16(tr.wte.weight), OF.weight_bf16(tr.wpe.weight)
         self.blocks = [blk.fused_params() for blk in tr.h]
         self.lnw, self.lnb = tr.ln_f.weight, tr.ln_f.bias
+        self.step_blocks, self.head = self.blocks, self.wte_k        # what ``rows`` and the LM head read
+        if dec is not None:
+            self.step_blocks, self.head = [(p, pairs) for (p, _), pairs in zip(self.blocks, dec.blocks)], dec.wte
 
     def prefill(self, idx, pl_dev):
         """idx int64 [B][P], pl_dev int32 [B] -> bf16 logits [B][V] at each prompt's last position; cache.lens = pl_dev"""
@@ -173,7 +211,7 @@ class Engine:
             x = TX.block_prefill(x, (B, Tp, c.n_head, c.eps), shadows, params, cache, layer)
         last = torch.arange(B, device=idx.device) * Tp + pl_dev.long() - 1
         xf, _, _ = K.layernorm_fwd(x.index_select(0, last), self.lnw, self.lnb, c.eps)
-        logits = BL.linear_fwd_decode(xf, self.wte_k)
+        logits = BL.linear_fwd_decode(xf, self.head)
         cache.lens.copy_(pl_dev)
         return logits
 
@@ -190,7 +228,7 @@ class Engine:
             x = TX.block_extend(x, (B, Tq, c.n_head, c.eps), shadows, params, cache, layer)
         last = torch.arange(B, device=idx.device) * Tq + pl_dev.long() - 1
         xf, _, _ = K.layernorm_fwd(x.index_select(0, last), self.lnw, self.lnb, c.eps)
-        logits = BL.linear_fwd_decode(xf, self.wte_k)
+        logits = BL.linear_fwd_decode(xf, self.head)
         cache.lens.add_(pl_dev)
         return logits
 
@@ -203,17 +241,24 @@ class Engine:
         c = self.config
         conf = (self.B, S, c.n_head, c.eps)
         x = K.embedding_decode(tok, pos, self.wte_k, self.wpe_k)
-        for layer, (params, shadows) in enumerate(self.blocks):
+        for layer, (params, shadows) in enumerate(self.step_blocks):
             x = TX.block_step(x, conf, shadows, params, self.cache, layer, S)
         xf, _, _ = K.layernorm_fwd(x, self.lnw, self.lnb, c.eps)
-        return BL.linear_fwd_decode(xf, self.wte_k) if S == 1 else K.gemm_skinny(xf, self.wte_k)
+        if S == 1 or self.head is not self.wte_k:
+            return BL.linear_fwd_decode(xf, self.head)
+        return K.gemm_skinny(xf, self.wte_k)
 
 
 class Reference:
-    """One call's CPU model (plain PyTorch, any head dim), the numerics reference of :class:`Engine`; ``lens`` int64 [B]"""
+    """One call's CPU model (plain PyTorch, any head dim), the numerics reference of :class:`Engine`; ``lens`` int64 [B].
+    ``dec`` (a :class:`DecodeWeights`): ``step`` and the logits after the prefill run with the dequantised weights dq in
+    place of the four block linears and the LM head; the prefill's blocks and the embeddings keep the originals."""
 
-    def __init__(self, model, B, Tmax):
+    def __init__(self, model, B, Tmax, dec=None):
         self.model, self.c, self.tr = model, model.config, model.transformer
+        dt = self.tr.wte.weight.dtype
+        self.dq = None if dec is None else [[dequantize_rows(*pr, dtype=dt) for pr in blk] for blk in dec.blocks]
+        self.head = model.lm_head.weight if dec is None else dequantize_rows(*dec.wte, dtype=dt)
         w, self.H, self.hd = self.tr.wte.weight, self.c.n_head, self.c.n_embd // self.c.n_head
         self.ks = [torch.zeros(B, self.H, Tmax, self.hd, device=w.device, dtype=w.dtype) for _ in self.tr.h]
         self.vs = [torch.zeros_like(k) for k in self.ks]
@@ -231,7 +276,7 @@ class Reference:
             y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
             x = x + blk.attn.c_proj(y.transpose(1, 2).reshape(B, P, c.n_embd))
             x = x + blk.mlp(blk.ln_2(x))
-        return self.model.lm_head(tr.ln_f(x[self.ar, self.lens - 1])).float()
+        return F.linear(tr.ln_f(x[self.ar, self.lens - 1]), self.head).float()
 
     def step(self, tok):
         """tok [B] at position lens[b] -> the next fp32 logits; lens += 1"""
@@ -239,21 +284,23 @@ class Reference:
         B = tok.shape[0]
         x = tr.wte(tok) + tr.wpe(lens.clamp(max=c.block_size - 1))                     # [B][D]
         vis = (self.keys[None, :] <= lens[:, None])[:, None, None, :]                   # keys 0..lens[b], new one included
-        for blk, kc, vc in zip(tr.h, self.ks, self.vs):
-            q, k, v = (t.view(B, H, hd) for t in blk.attn.c_attn(blk.ln_1(x)).split(c.n_embd, dim=1))
+        for i, (blk, kc, vc) in enumerate(zip(tr.h, self.ks, self.vs)):
+            mods = (blk.attn.c_attn, blk.attn.c_proj, blk.mlp.c_fc, blk.mlp.c_proj)
+            wq, wp, wf, wf2 = (m.weight for m in mods) if self.dq is None else self.dq[i]
+            q, k, v = (t.view(B, H, hd) for t in F.linear(blk.ln_1(x), wq, mods[0].bias).split(c.n_embd, dim=1))
             kc[ar, :, lens], vc[ar, :, lens] = k, v
             y = F.scaled_dot_product_attention(q.unsqueeze(2), kc, vc, attn_mask=vis)
-            x = x + blk.attn.c_proj(y.reshape(B, c.n_embd))
-            x = x + blk.mlp(blk.ln_2(x))
+            x = x + F.linear(y.reshape(B, c.n_embd), wp, mods[1].bias)
+            x = x + F.linear(F.gelu(F.linear(blk.ln_2(x), wf, mods[2].bias), approximate="tanh"), wf2, mods[3].bias)
         lens.add_(1)
-        return self.model.lm_head(tr.ln_f(x)).float()
+        return F.linear(tr.ln_f(x), self.head).float()
 
 
-def fused_stepper(model, idx, pl_dev, max_new_tokens, graph=False, cache=None, resume=False):
+def fused_stepper(model, idx, pl_dev, max_new_tokens, graph=False, cache=None, resume=False, dec=None):
     """GPU: prefill -> (fp32 logits [B][V] at each prompt's last position, step(tok) -> the next logits, in one fp32
     buffer).  The engine of the torch-sampler loop: the token comes from the host side of the loop."""
     B, P = idx.shape
-    eng = Engine(model, B, P, max_new_tokens, 1, cache, resume)
+    eng = Engine(model, B, P, max_new_tokens, 1, cache, resume, dec)
     logits16 = eng.ingest(idx, pl_dev, resume)
     tok_buf = torch.zeros(B, dtype=torch.int64, device=idx.device)
     logits = logits16.float()
@@ -330,12 +377,12 @@ def _speculate_device(eng, r, pl_dev, out, logit_buf):
     return {"verify_steps": steps, "stats": stats.tolist()}
 
 
-def _speculate_reference(model, r, idx, pl_dev, out):
+def _speculate_reference(model, r, idx, pl_dev, out, dec=None):
     """CPU: the same loop on ops.speculate's references.  A step's S verify logits come from S successive reference steps
     (a position the row never reaches is clamped to the last slot, which no emitted token reads); then lens = accepted"""
     B, P, N, S = r.B, r.P, r.N, r.S
     Tmax = max(r.pl) + N
-    ref = Reference(model, B, Tmax)
+    ref = Reference(model, B, Tmax, dec)
     finished = torch.zeros(B, dtype=torch.uint8, device=idx.device) if r.eos is not None else None
     out[:, P], _, _ = sample_reference(ref.prefill(idx, pl_dev), state=(r.seed, 0), finished=finished, eos_token=r.eos,
                                        **r.draw)
@@ -363,8 +410,9 @@ def generate(model, idx, max_new_tokens, **kw):
     B, P, N = r.B, r.P, r.N
     idx = idx.long()
     out = torch.cat([idx, idx.new_zeros(B, N)], 1)
+    dec = DecodeWeights.of(model, r.decode_weights) if N else None      # an ingest-only call draws from no logits
     if N == 0 and r.resume:                             # chunked prefill: the ingest is the whole call
-        Engine(model, B, P, 0, r.S or 1, r.cache, True).extend(idx, torch.tensor(r.pl, device=idx.device,
+        Engine(model, B, P, 0, r.S or 1, r.cache, True, dec).extend(idx, torch.tensor(r.pl, device=idx.device,
                                                                                  dtype=torch.int32))
     if N == 0:
         if r.return_stats:
@@ -374,18 +422,18 @@ def generate(model, idx, max_new_tokens, **kw):
     if r.guess is not None:
         r = r._replace(guess=r.guess.to(idx.device).contiguous())
     if r.seed is not None and idx.is_cuda:         # the sampling kernel is inside the step: the loop is on the device
-        eng = Engine(model, B, P, N, r.S or 1, r.cache, r.resume)
+        eng = Engine(model, B, P, N, r.S or 1, r.cache, r.resume, dec)
         logit_buf = eng.ingest(idx, pl_dev, r.resume)
         res = _speculate_device(eng, r, pl_dev, out, logit_buf) if r.S else _device_loop(eng, r, out, logit_buf)
         return (out, res) if r.return_logits or r.return_stats else out
     if r.S:
-        stats = _speculate_reference(model, r, idx, pl_dev, out)
+        stats = _speculate_reference(model, r, idx, pl_dev, out, dec)
         return (out, stats) if r.return_stats else out
     # the token is drawn on the host side of the loop: the torch sampler on both devices, the device sampler's reference
     if idx.is_cuda:
-        logits, step = fused_stepper(model, idx, pl_dev, N, r.graph, r.cache, r.resume)
+        logits, step = fused_stepper(model, idx, pl_dev, N, r.graph, r.cache, r.resume, dec)
     else:
-        ref = Reference(model, B, max(r.pl) + N)
+        ref = Reference(model, B, max(r.pl) + N, dec)
         logits, step = ref.prefill(idx, pl_dev), ref.step
     finished = torch.zeros(B, dtype=torch.bool, device=idx.device)      # rows that have emitted eos_token
     if r.seed is not None:                                              # sample_reference: uint8 flags, None without eos
@@ -419,7 +467,9 @@ class Session:
     it: a turn costs its own tokens against the cache, not the whole history again.  On the CPU there is no cache: the
     same call re-runs ``generate`` on the concatenated history, which is the definition the GPU path is held to."""
 
-    def __init__(self, model, B, max_len, S=1):
+    def __init__(self, model, B, max_len, S=1, decode_weights="bf16"):
+        if decode_weights not in ("bf16", "fp8"):
+            raise ValueError(f"session: decode_weights must be 'bf16' or 'fp8', got {decode_weights!r}")
         if B < 1 or not 1 <= max_len <= model.config.block_size:
             raise ValueError(f"session: B >= 1 and 1 <= max_len <= block size {model.config.block_size}, got B = {B}, "
                              f"max_len = {max_len}")
@@ -427,6 +477,8 @@ class Session:
         self.device = model.transformer.wte.weight.device
         self.history, self.cached = [[] for _ in range(B)], [0] * B
         self.cache = TX.KVCache(model, B, max_len, self.device, S=S) if self.device.type == "cuda" else None
+        # quantised once, here: every turn runs on this snapshot of the weights
+        self.sampling = {"decode_weights": DecodeWeights(model)} if decode_weights == "fp8" else {}
 
     def generate(self, turns, max_new_tokens, *, eos_token=None, **sampling):
         """``turns``: B token sequences (lists or 1-D tensors), row b's next turn; it may be empty only where the row has
@@ -434,6 +486,7 @@ class Session:
         generator, graph.  -> the new tokens per row, B lists, each cut after its first ``eos_token``."""
         if len(turns) != self.B:
             raise ValueError(f"session: {self.B} turns expected, got {len(turns)}")
+        sampling = {**self.sampling, **sampling}
         for bad in ("cache", "resume", "prompt_lens", "return_logits", "return_stats"):
             if bad in sampling:
                 raise ValueError(f"session: {bad} is the session's own argument of generate")

@@ -303,7 +303,7 @@ class GPT2(nn.Module):
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, *, temperature=1.0, top_k=None, eos_token=None, prompt_lens=None,
                  generator=None, graph=False, return_logits=False, cache=None, top_p=None, sampler="torch", seed=None,
-                 speculate=None, draft="ngram", ngram=3, return_stats=False, resume=False):
+                 speculate=None, draft="ngram", ngram=3, return_stats=False, resume=False, decode_weights="bf16"):
         """Sample ``max_new_tokens`` tokens after the prompts ``idx`` int [B][P] with a key/value cache: one prefill over
         the prompt, then one single-token step per new token (GPU: ``ops.transformer.block_step`` on the decode
         attention kernel of ``csrc/kernels/attention_decode.hip``; CPU: plain PyTorch in fp32 with per-layer k, v lists,
@@ -322,7 +322,19 @@ class GPT2(nn.Module):
         with torch.cuda.graph on a single stream and replayed; the cache length lives on the device, so a replay follows
         it.  ``cache`` (GPU): an ``ops.transformer.KVCache`` of this batch size with Tmax >= kv_cache_len(P,
         max_new_tokens) to reuse; it is reset first.  ``config.doc_mask_eot`` is not applied: a prompt is one document.
-        The block linears are bf16 even with ``config.fp8``.
+        The block linears do not follow ``config.fp8``: their storage in generation is ``decode_weights``.
+
+        ``decode_weights="fp8"``: weight-only fp8 decode.  The four linears of every block and the tied LM head are
+        quantised when the call starts, from their bf16 values, to OCP e4m3fn codes with one power-of-two scale per
+        output row (``ops/quant.py``; GPU: the quantiser of ``csrc/kernels/gemm_skinny_fp8.hip``), and every decode step,
+        verify step and LM-head GEMM of the call streams the codes at one byte per element (``ops.kernels.
+        gemm_skinny_fp8``; activations stay bf16, accumulation fp32).  The prefill / extend blocks and the embeddings
+        keep the bf16 weights.  The dequantised weights are exactly bf16 numbers, so the result is that of a bf16 model
+        with those weights in the step: the CPU path computes exactly that (its reference), and speculation, graph
+        replay and resume stay bit for bit what they are without them.  The GPU path needs tuning ``decode_skinny``,
+        B * (speculate or 1) <= 64 and n_embd % 16 == 0.  The default ``"bf16"`` quantises nothing and runs no new kernel.
+        Every ``"fp8"`` call quantises again; a ``generation.DecodeWeights(model)`` made once may be passed instead (a
+        snapshot of the weights at that moment; :meth:`session` keeps one).
 
         ``top_p`` (both samplers): nucleus sampling after top-k.  ``sampler="device"`` draws with the counter-based
         generator instead of ``generator``: step i of row b uses u(``seed``, i, b), and the token is the one defined in
@@ -358,12 +370,14 @@ class GPT2(nn.Module):
         return G.generate(self, idx, max_new_tokens, temperature=temperature, top_k=top_k, eos_token=eos_token,
                           prompt_lens=prompt_lens, generator=generator, graph=graph, return_logits=return_logits,
                           cache=cache, top_p=top_p, sampler=sampler, seed=seed, speculate=speculate, draft=draft,
-                          ngram=ngram, return_stats=return_stats, resume=resume)
+                          ngram=ngram, return_stats=return_stats, resume=resume, decode_weights=decode_weights)
 
-    def session(self, B, max_len, S=1):
+    def session(self, B, max_len, S=1, decode_weights="bf16"):
         """A :class:`generation.Session`: B conversations of up to ``max_len`` tokens whose key/value cache is kept from
-        one ``session.generate(turns, max_new_tokens, ...)`` to the next (``S``: the largest ``speculate`` to be used)"""
-        return G.Session(self, B, max_len, S)
+        one ``session.generate(turns, max_new_tokens, ...)`` to the next (``S``: the largest ``speculate`` to be used).
+        ``decode_weights="fp8"`` (see :meth:`generate`) quantises once, here; every turn reuses that set, which is a
+        snapshot of the weights at this moment: a later update of the model does not reach it."""
+        return G.Session(self, B, max_len, S, decode_weights)
 
     def _forward_reference(self, idx, targets=None, doc=None, drop=None):
         B, T = idx.shape

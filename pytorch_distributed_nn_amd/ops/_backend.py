@@ -136,6 +136,9 @@ _SIGS = {
     "pdnn_gemm_nt_ex": [P, L, P, L, P, L, I, I, I, F, P, I, P, P, P, I, P],
     "pdnn_gemm_skinny": [P, L, P, P, L, I, I, I, P, I, P, P],
     "pdnn_gemm_skinny_plan": [I, I],
+    "pdnn_quant_rows_e4m3": [P, I, I, P, P, P],
+    "pdnn_gemm_skinny_fp8": [P, L, P, P, P, L, I, I, I, P, I, P, P],
+    "pdnn_gemm_skinny_fp8_plan": [I, I],
     "pdnn_layernorm_fwd": [P, P, P, P, P, P, I, I, F, P],
     "pdnn_layernorm_bwd_blocks": [I],
     "pdnn_layernorm_bwd": [P, P, P, P, P, P, P, P, I, I, I, P],

@@ -1387,6 +1387,51 @@ def gemm_skinny(x, w, bias=None, act=0, res=None, out=None):
     return out
 
 
+def quant_rows_e4m3(w):
+    """w bf16 [N][K] contiguous -> (q uint8 [N][K] e4m3fn codes, inv fp32 [N]): the format of ops/quant.py, computed by
+    csrc/kernels/gemm_skinny_fp8.hip.  K % 16 == 0, N % 8 == 0."""
+    _chk(torch.is_tensor(w) and w.dtype == BF16 and w.is_cuda and w.dim() == 2 and w.is_contiguous()
+         and w.data_ptr() % 16 == 0, "quant_rows_e4m3: w must be a contiguous 16-byte aligned 2-D CUDA bf16 tensor")
+    N, K = w.shape
+    _chk(K >= 16 and K % 16 == 0 and N >= 8 and N % 8 == 0, f"quant_rows_e4m3: K % 16 == 0, N % 8 == 0, got {tuple(w.shape)}")
+    q = torch.empty(N, K, device=w.device, dtype=torch.uint8)
+    inv = torch.empty(N, device=w.device, dtype=F32)
+    call("pdnn_quant_rows_e4m3", ptr(w), N, K, ptr(q), ptr(inv), stream())
+    return q, inv
+
+
+def gemm_skinny_fp8(x, q, inv, bias=None, act=0, res=None, out=None):
+    """:func:`gemm_skinny` on a weight stored as e4m3fn codes: y = act(x @ dq^T + bias) (+res), dq[n][k] = value(q[n][k])
+    inv[n] (csrc/kernels/gemm_skinny_fp8.hip).  x bf16 [M][K] (row-strided), 1 <= M <= 64, q uint8 [N][K] contiguous, inv
+    fp32 [N], K % 16 == 0, N % 8 == 0; bias, act, res, out as there.  Row b does not depend on M or on the other rows."""
+    _chk(torch.is_tensor(x) and x.dtype == BF16 and x.is_cuda and x.dim() == 2 and x.data_ptr() % 16 == 0,
+         "gemm_skinny_fp8: x must be a 16-byte aligned 2-D CUDA bf16 tensor")
+    _chk(torch.is_tensor(q) and q.dtype == torch.uint8 and q.dim() == 2 and q.device == x.device and q.is_contiguous()
+         and q.data_ptr() % 16 == 0, "gemm_skinny_fp8: q must be contiguous uint8 [N][K] on x's device")
+    M, K = x.shape
+    N = q.shape[0]
+    _chk(1 <= M <= SKINNY_ROWS, f"gemm_skinny_fp8: 1 <= M <= {SKINNY_ROWS}, got M = {M}")
+    _chk(q.shape[1] == K and K >= 16 and N >= 8 and K % 16 == 0 and N % 8 == 0,
+         f"gemm_skinny_fp8: {tuple(x.shape)} {tuple(q.shape)}")
+    _chk(torch.is_tensor(inv) and inv.dtype == F32 and inv.shape == (N,) and inv.is_contiguous() and inv.device == x.device,
+         f"gemm_skinny_fp8: inv must be contiguous fp32 [{N}]")
+    _chk(x.stride(1) == 1 and x.stride(0) >= K and x.stride(0) % 8 == 0, "gemm_skinny_fp8: x rows contiguous, row stride % 8 == 0")
+    _chk(act in (0, 2), f"gemm_skinny_fp8: act must be 0 or 2 (GELU), got {act!r}")
+    _chk(bias is None or (bias.dtype == F32 and bias.shape == (N,) and bias.is_contiguous()
+                          and bias.device == x.device), f"gemm_skinny_fp8: bias must be contiguous fp32 [{N}]")
+    if out is None:
+        out = torch.empty(M, N, device=x.device, dtype=BF16)
+    _chk(out.dtype == BF16 and out.shape == (M, N) and out.device == x.device and out.stride(1) == 1
+         and out.stride(0) >= N and out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0,
+         f"gemm_skinny_fp8: out must be bf16 [{M}][{N}], rows contiguous, row stride % 8 == 0")
+    _chk(res is None or (res.dtype == BF16 and res.device == x.device and res.shape == out.shape
+                         and res.stride() == out.stride() and res.data_ptr() % 16 == 0),
+         "gemm_skinny_fp8: res must be bf16 of out's shape and strides")
+    call("pdnn_gemm_skinny_fp8", ptr(x), x.stride(0), ptr(q), ptr(inv), ptr(out), out.stride(0), M, N, K, ptr(bias),
+         int(act), ptr(res), stream())
+    return out
+
+
 def layernorm_fwd(x, g, b, eps):
     _bf16_c(x, "layernorm.x")
     _chk(x.dim() == 2, "layernorm: x must be 2-D")

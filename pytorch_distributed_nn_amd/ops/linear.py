@@ -36,7 +36,13 @@ def linear_fwd(x, wk, bias=None, act=0, aux=None, res=None):
 def linear_fwd_decode(x, wk, bias=None, act=0, res=None):
     """:func:`linear_fwd` for the M = B rows of a decode step: up to ``kernels.SKINNY_MAX_M`` rows run the
     weight-streaming kernel (``kernels.gemm_skinny``, csrc/kernels/gemm_skinny.hip) unless tuning ``decode_skinny``
-    is 0; everything else is :func:`linear_fwd`."""
+    is 0; everything else is :func:`linear_fwd`.  ``wk`` may also be a pair (q, inv), the weight stored as e4m3fn
+    codes with row scales (ops/quant.py): it runs ``kernels.gemm_skinny_fp8`` for every M up to ``kernels.SKINNY_ROWS``
+    and has no other engine, so more rows are refused."""
+    if isinstance(wk, tuple):
+        if x.shape[0] > K.SKINNY_ROWS:
+            raise ValueError(f"linear_fwd_decode: fp8 decode weights take at most {K.SKINNY_ROWS} rows, got {x.shape[0]}")
+        return K.gemm_skinny_fp8(x, wk[0], wk[1], bias=bias, act=act, res=res)
     if _tuning.get("decode_skinny") and x.is_cuda and x.shape[0] <= K.SKINNY_MAX_M:
         return K.gemm_skinny(x, wk, bias=bias, act=act, res=res)
     return linear_fwd(x, wk, bias=bias, act=act, res=res)

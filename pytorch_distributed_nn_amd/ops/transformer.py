@@ -555,7 +555,9 @@ def block_step(x, conf, shadows, params, cache, layer, S=1):
     """One block on the S new tokens per sequence: x bf16 [B*S][D] -> x2, row b*S + j at position cache.lens[b] + j; the
     decode attention also stores the new k, v rows.  No host read-back; cache.lens unchanged.  S == 1, a decode step:
     BL.linear_fwd_decode and K.attn_decode.  S > 1, a speculative verify step: K.attn_decode_multi, and K.gemm_skinny
-    for every M = B*S <= K.SKINNY_ROWS, whose row bits do not depend on M: a row gets the bits of the S == 1 step."""
+    for every M = B*S <= K.SKINNY_ROWS, whose row bits do not depend on M: a row gets the bits of the S == 1 step.
+    ``shadows`` of pairs (q, inv) (ops/quant.py) run the four linears on K.gemm_skinny_fp8 for S == 1 and S > 1 alike: the
+    same kernel, row bits independent of M."""
     B, _, H, eps = conf[:4]
     if S == 1:
         lin, attn, multi = BL.linear_fwd_decode, K.attn_decode, {}
@@ -564,6 +566,8 @@ def block_step(x, conf, shadows, params, cache, layer, S=1):
             raise ValueError(f"block_verify: {x.shape[0]} rows for B = {B}, S = {S} (cache S = {cache.S}, at most "
                              f"{K.SKINNY_ROWS} rows)")
         lin, attn, multi = K.gemm_skinny, K.attn_decode_multi, {"S": S}
+    if isinstance(shadows[0], tuple):       # fp8 decode weights, pairs (q, inv): one kernel for every row count
+        lin = BL.linear_fwd_decode
     return _block_infer(x, eps, shadows, params, lin, attn, cache.k[layer], cache.v[layer], cache.lens, chunk=cache.chunk,
                         part=cache.part, scale=1.0 / math.sqrt(x.shape[1] // H), **multi)
 

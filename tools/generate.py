@@ -60,6 +60,9 @@ def build_parser():
     ap.add_argument("--chunk", type=int, default=None, metavar="C",
                     help="ingest the prompt in pieces of C tokens through generate(resume=True) on a kept cache before "
                          "sampling (GPU; the CPU path keeps no cache and runs the prompt in one piece)")
+    ap.add_argument("--decode-weights", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: the decode steps stream the block linears and the LM head as e4m3 codes with row scales "
+                         "(weight-only; GPT2.generate)")
     return ap
 
 
@@ -92,7 +95,7 @@ def main(argv=None):
     if args.chunk is not None and args.chunk < 1:
         raise SystemExit(f"--chunk {args.chunk}: expected a positive number of tokens")
     kw = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, eos_token=args.eos_token,
-              graph=args.graph and dev.type == "cuda", **draw)
+              graph=args.graph and dev.type == "cuda", decode_weights=args.decode_weights, **draw)
     idx = idx.to(dev)
     try:
         if args.chunk is not None and dev.type == "cuda":
