@@ -260,6 +260,7 @@ __global__ void __launch_bounds__(NTD) attn_decode_multi_kernel(const bf16_t* __
 }
 
 // one block (64 threads = the 64 dims) per (b, h): out = sum_i w_i o_i / sum_i w_i l_i, w_i = exp2(m_i - M), chunk order
+// (attention_cache_fp8.hip holds a copy of this kernel and of chunk_tail: a fix here belongs there too)
 __global__ void __launch_bounds__(64) attn_decode_combine_kernel(const float* __restrict__ part, bf16_t* __restrict__ out,
                                                                  int nchunk) {
     const int bh = blockIdx.x, d = threadIdx.x;

@@ -31,6 +31,9 @@
 //     limit are this call's new keys, which the append has written.
 // Padding query rows (a turn shorter than Tq) produce values nobody reads; causality keeps them invisible to real rows.
 //
+// attention_cache_fp8.hip holds a copy of this kernel behind a converting tile loader (pdnn_attn_extend_fp8, held to this
+// one bit for bit): a fix here belongs there too.
+//
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950):
 //   attn_extend_kernel       122 VGPRs (0 AGPRs), 32768 bytes LDS, scratch 0, 4 waves / SIMD
 //   kv_cache_append_kernel    22 VGPRs, 0 bytes LDS, scratch 0

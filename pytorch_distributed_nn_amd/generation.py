@@ -38,9 +38,10 @@ def sample(logits, temperature, top_k, generator, top_p=None):
 
 
 # one checked call: N = max_new_tokens, pl = the B prompt lengths, draw = dict(temperature, top_k, top_p), seed masked to
-# 63 bits (sampler="device", else None), S = speculate or None, guess = the draft table or None (n-gram drafts)
+# 63 bits (sampler="device", else None), S = speculate or None, guess = the draft table or None (n-gram drafts), kv = the
+# cache's storage, "bf16" or "fp8"
 Request = namedtuple("Request", "B P N pl draw eos generator seed S guess ngram graph return_logits return_stats cache "
-                     "resume decode_weights", defaults=(False, "bf16"))
+                     "resume decode_weights kv", defaults=(False, "bf16", "bf16"))
 
 
 class DecodeWeights:
@@ -69,7 +70,7 @@ class DecodeWeights:
 
 def check_args(c, idx, max_new_tokens, *, temperature, top_k, eos_token, prompt_lens, generator, graph,
                return_logits, cache, top_p, sampler, seed, speculate, draft, ngram, return_stats, resume=False,
-               decode_weights="bf16"):
+               decode_weights="bf16", kv_cache=None):
     """``generate``'s arguments and the model's config ``c`` -> :class:`Request`, or the first refusal in this order"""
     if idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
         raise ValueError(f"generate: idx must be [B][P] with B, P >= 1, got {tuple(idx.shape)}")
@@ -130,9 +131,14 @@ def check_args(c, idx, max_new_tokens, *, temperature, top_k, eos_token, prompt_
         raise ValueError(f"generate: decode_weights='fp8' on the GPU needs tuning decode_skinny on, B * speculate <= "
                          f"{K.SKINNY_ROWS} (the fp8 weights have the skinny kernel only) and n_embd % 16 == 0; got "
                          f"decode_skinny = {tuning.get('decode_skinny')!r}, B = {B}, S = {S}, n_embd = {c.n_embd}")
+    if kv_cache not in (None, "bf16", "fp8"):
+        raise ValueError(f"generate: kv_cache must be 'bf16' or 'fp8', got {kv_cache!r}")
+    have = getattr(cache, "dtype", None)                # None: the cache follows a passed cache=, else it is bf16
+    if kv_cache is not None and have is not None and have != kv_cache:
+        raise ValueError(f"generate: kv_cache={kv_cache!r} with a cache= of dtype {have!r}")
     return Request(B, P, max_new_tokens, pl, dict(temperature=float(temperature), top_k=top_k, top_p=top_p), eos_token,
                    generator, int(seed) & ((1 << 63) - 1) if sampler == "device" else None, S, guess, ngram, graph,
-                   return_logits, return_stats, cache, bool(resume), decode_weights)
+                   return_logits, return_stats, cache, bool(resume), decode_weights, kv_cache or have or "bf16")
 
 
 def check_resume(c, idx, B, pl, N, S, cache):
@@ -175,19 +181,22 @@ class Replay:
 class Engine:
     """One call's GPU model: the cache (``cache`` if it fits, reset; else a new one), bf16 shadows, block parameters.
     ``dec`` (a :class:`DecodeWeights`): ``rows`` and every LM-head GEMM run on its fp8 pairs; prefill and extend blocks
-    keep the bf16 shadows."""
+    keep the bf16 shadows.  ``kv``: the storage of a new cache (check_args has held a passed one against it); the blocks
+    take their attention kernels from the cache."""
 
-    def __init__(self, model, B, P, N, S=1, cache=None, resume=False, dec=None):
+    def __init__(self, model, B, P, N, S=1, cache=None, resume=False, dec=None, kv="bf16"):
         self.config, tr = model.config, model.transformer
         dev = tr.wte.weight.device
         Tneed = model.kv_cache_len(P, N + (S if S > 1 else 0))       # rejected drafts occupy slots past the accepted length
         if resume:                                      # check_resume has held the kept cache against this call
             pass
         elif cache is None:
-            cache = TX.KVCache(model, B, Tneed, dev, S=S)
+            cache = TX.KVCache(model, B, Tneed, dev, S=S, dtype=kv)
         elif cache.B != B or cache.Tmax < Tneed or cache.k.device != dev or cache.S < S:
             raise ValueError(f"generate: cache of B = {cache.B}, Tmax = {cache.Tmax}, S = {cache.S} on {cache.k.device} does "
                              f"not fit B = {B}, Tmax >= {Tneed}, S >= {S} on {dev}")
+        if cache.dtype != kv:
+            raise ValueError(f"generate: kv_cache={kv!r} with a cache of dtype {cache.dtype!r}")
         if not resume:
             cache.reset()
         self.B, self.cache = B, cache
@@ -252,10 +261,15 @@ class Engine:
 class Reference:
     """One call's CPU model (plain PyTorch, any head dim), the numerics reference of :class:`Engine`; ``lens`` int64 [B].
     ``dec`` (a :class:`DecodeWeights`): ``step`` and the logits after the prefill run with the dequantised weights dq in
-    place of the four block linears and the LM head; the prefill's blocks and the embeddings keep the originals."""
+    place of the four block linears and the LM head; the prefill's blocks and the embeddings keep the originals.
+    ``kv="fp8"``: every K and V row (one layer, sequence, head, slot) is stored as dequantize_rows(*
+    quantize_rows_reference(row)), and a step attends to its new token's stored row; the prefill's own attention reads the
+    prompt's K and V as they are."""
 
-    def __init__(self, model, B, Tmax, dec=None):
+    def __init__(self, model, B, Tmax, dec=None, kv="bf16"):
         self.model, self.c, self.tr = model, model.config, model.transformer
+        self.rt = (lambda t: t) if kv == "bf16" else \
+            (lambda t: dequantize_rows(*quantize_rows_reference(t.reshape(-1, t.shape[-1])), dtype=t.dtype).view_as(t))
         dt = self.tr.wte.weight.dtype
         self.dq = None if dec is None else [[dequantize_rows(*pr, dtype=dt) for pr in blk] for blk in dec.blocks]
         self.head = model.lm_head.weight if dec is None else dequantize_rows(*dec.wte, dtype=dt)
@@ -272,7 +286,7 @@ class Reference:
         x = tr.wte(idx) + tr.wpe(torch.arange(P, device=idx.device).clamp(max=c.block_size - 1))
         for blk, kc, vc in zip(tr.h, self.ks, self.vs):
             q, k, v = (t.view(B, P, H, hd).transpose(1, 2) for t in blk.attn.c_attn(blk.ln_1(x)).split(c.n_embd, dim=2))
-            kc[:, :, :P], vc[:, :, :P] = k, v
+            kc[:, :, :P], vc[:, :, :P] = self.rt(k), self.rt(v)
             y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
             x = x + blk.attn.c_proj(y.transpose(1, 2).reshape(B, P, c.n_embd))
             x = x + blk.mlp(blk.ln_2(x))
@@ -288,7 +302,7 @@ class Reference:
             mods = (blk.attn.c_attn, blk.attn.c_proj, blk.mlp.c_fc, blk.mlp.c_proj)
             wq, wp, wf, wf2 = (m.weight for m in mods) if self.dq is None else self.dq[i]
             q, k, v = (t.view(B, H, hd) for t in F.linear(blk.ln_1(x), wq, mods[0].bias).split(c.n_embd, dim=1))
-            kc[ar, :, lens], vc[ar, :, lens] = k, v
+            kc[ar, :, lens], vc[ar, :, lens] = self.rt(k), self.rt(v)
             y = F.scaled_dot_product_attention(q.unsqueeze(2), kc, vc, attn_mask=vis)
             x = x + F.linear(y.reshape(B, c.n_embd), wp, mods[1].bias)
             x = x + F.linear(F.gelu(F.linear(blk.ln_2(x), wf, mods[2].bias), approximate="tanh"), wf2, mods[3].bias)
@@ -296,11 +310,11 @@ class Reference:
         return F.linear(tr.ln_f(x), self.head).float()
 
 
-def fused_stepper(model, idx, pl_dev, max_new_tokens, graph=False, cache=None, resume=False, dec=None):
+def fused_stepper(model, idx, pl_dev, max_new_tokens, graph=False, cache=None, resume=False, dec=None, kv="bf16"):
     """GPU: prefill -> (fp32 logits [B][V] at each prompt's last position, step(tok) -> the next logits, in one fp32
     buffer).  The engine of the torch-sampler loop: the token comes from the host side of the loop."""
     B, P = idx.shape
-    eng = Engine(model, B, P, max_new_tokens, 1, cache, resume, dec)
+    eng = Engine(model, B, P, max_new_tokens, 1, cache, resume, dec, kv)
     logits16 = eng.ingest(idx, pl_dev, resume)
     tok_buf = torch.zeros(B, dtype=torch.int64, device=idx.device)
     logits = logits16.float()
@@ -382,7 +396,7 @@ def _speculate_reference(model, r, idx, pl_dev, out, dec=None):
     (a position the row never reaches is clamped to the last slot, which no emitted token reads); then lens = accepted"""
     B, P, N, S = r.B, r.P, r.N, r.S
     Tmax = max(r.pl) + N
-    ref = Reference(model, B, Tmax, dec)
+    ref = Reference(model, B, Tmax, dec, r.kv)
     finished = torch.zeros(B, dtype=torch.uint8, device=idx.device) if r.eos is not None else None
     out[:, P], _, _ = sample_reference(ref.prefill(idx, pl_dev), state=(r.seed, 0), finished=finished, eos_token=r.eos,
                                        **r.draw)
@@ -412,7 +426,7 @@ def generate(model, idx, max_new_tokens, **kw):
     out = torch.cat([idx, idx.new_zeros(B, N)], 1)
     dec = DecodeWeights.of(model, r.decode_weights) if N else None      # an ingest-only call draws from no logits
     if N == 0 and r.resume:                             # chunked prefill: the ingest is the whole call
-        Engine(model, B, P, 0, r.S or 1, r.cache, True, dec).extend(idx, torch.tensor(r.pl, device=idx.device,
+        Engine(model, B, P, 0, r.S or 1, r.cache, True, dec, r.kv).extend(idx, torch.tensor(r.pl, device=idx.device,
                                                                                  dtype=torch.int32))
     if N == 0:
         if r.return_stats:
@@ -422,7 +436,7 @@ def generate(model, idx, max_new_tokens, **kw):
     if r.guess is not None:
         r = r._replace(guess=r.guess.to(idx.device).contiguous())
     if r.seed is not None and idx.is_cuda:         # the sampling kernel is inside the step: the loop is on the device
-        eng = Engine(model, B, P, N, r.S or 1, r.cache, r.resume, dec)
+        eng = Engine(model, B, P, N, r.S or 1, r.cache, r.resume, dec, r.kv)
         logit_buf = eng.ingest(idx, pl_dev, r.resume)
         res = _speculate_device(eng, r, pl_dev, out, logit_buf) if r.S else _device_loop(eng, r, out, logit_buf)
         return (out, res) if r.return_logits or r.return_stats else out
@@ -431,9 +445,9 @@ def generate(model, idx, max_new_tokens, **kw):
         return (out, stats) if r.return_stats else out
     # the token is drawn on the host side of the loop: the torch sampler on both devices, the device sampler's reference
     if idx.is_cuda:
-        logits, step = fused_stepper(model, idx, pl_dev, N, r.graph, r.cache, r.resume, dec)
+        logits, step = fused_stepper(model, idx, pl_dev, N, r.graph, r.cache, r.resume, dec, r.kv)
     else:
-        ref = Reference(model, B, max(r.pl) + N, dec)
+        ref = Reference(model, B, max(r.pl) + N, dec, r.kv)
         logits, step = ref.prefill(idx, pl_dev), ref.step
     finished = torch.zeros(B, dtype=torch.bool, device=idx.device)      # rows that have emitted eos_token
     if r.seed is not None:                                              # sample_reference: uint8 flags, None without eos
@@ -467,18 +481,20 @@ class Session:
     it: a turn costs its own tokens against the cache, not the whole history again.  On the CPU there is no cache: the
     same call re-runs ``generate`` on the concatenated history, which is the definition the GPU path is held to."""
 
-    def __init__(self, model, B, max_len, S=1, decode_weights="bf16"):
-        if decode_weights not in ("bf16", "fp8"):
-            raise ValueError(f"session: decode_weights must be 'bf16' or 'fp8', got {decode_weights!r}")
+    def __init__(self, model, B, max_len, S=1, decode_weights="bf16", kv_cache="bf16"):
+        if decode_weights not in ("bf16", "fp8") or kv_cache not in ("bf16", "fp8"):
+            raise ValueError(f"session: decode_weights and kv_cache must be 'bf16' or 'fp8', got {decode_weights!r}, "
+                             f"{kv_cache!r}")
         if B < 1 or not 1 <= max_len <= model.config.block_size:
             raise ValueError(f"session: B >= 1 and 1 <= max_len <= block size {model.config.block_size}, got B = {B}, "
                              f"max_len = {max_len}")
         self.model, self.B, self.max_len = model, B, max_len
         self.device = model.transformer.wte.weight.device
         self.history, self.cached = [[] for _ in range(B)], [0] * B
-        self.cache = TX.KVCache(model, B, max_len, self.device, S=S) if self.device.type == "cuda" else None
+        self.cache = TX.KVCache(model, B, max_len, self.device, S=S, dtype=kv_cache) if self.device.type == "cuda" else None
         # quantised once, here: every turn runs on this snapshot of the weights
         self.sampling = {"decode_weights": DecodeWeights(model)} if decode_weights == "fp8" else {}
+        self.sampling["kv_cache"] = kv_cache
 
     def generate(self, turns, max_new_tokens, *, eos_token=None, **sampling):
         """``turns``: B token sequences (lists or 1-D tensors), row b's next turn; it may be empty only where the row has

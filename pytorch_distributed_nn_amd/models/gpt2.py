@@ -303,7 +303,8 @@ class GPT2(nn.Module):
     @torch.no_grad()
     def generate(self, idx, max_new_tokens, *, temperature=1.0, top_k=None, eos_token=None, prompt_lens=None,
                  generator=None, graph=False, return_logits=False, cache=None, top_p=None, sampler="torch", seed=None,
-                 speculate=None, draft="ngram", ngram=3, return_stats=False, resume=False, decode_weights="bf16"):
+                 speculate=None, draft="ngram", ngram=3, return_stats=False, resume=False, decode_weights="bf16",
+                 kv_cache=None):
         """Sample ``max_new_tokens`` tokens after the prompts ``idx`` int [B][P] with a key/value cache: one prefill over
         the prompt, then one single-token step per new token (GPU: ``ops.transformer.block_step`` on the decode
         attention kernel of ``csrc/kernels/attention_decode.hip``; CPU: plain PyTorch in fp32 with per-layer k, v lists,
@@ -335,6 +336,17 @@ class GPT2(nn.Module):
         B * (speculate or 1) <= 64 and n_embd % 16 == 0.  The default ``"bf16"`` quantises nothing and runs no new kernel.
         Every ``"fp8"`` call quantises again; a ``generation.DecodeWeights(model)`` made once may be passed instead (a
         snapshot of the weights at that moment; :meth:`session` keeps one).
+
+        ``kv_cache="fp8"``: the key/value cache holds OCP e4m3fn codes with one power-of-two scale per 64-element row of K
+        and of V (one layer, sequence, head and slot; the rule of ``ops/quant.py``), 68 bytes per row instead of 128
+        (``ops.transformer.KVCache(dtype="fp8")``; the kernels of ``csrc/kernels/attention_cache_fp8.hip``).  Every key
+        and value enters decode and extend attention as its dequantised row, whether it comes from the cache or is the
+        step's own new token, so a key has one value in the step that creates it and in every later one: speculation,
+        graph replay and resume stay bit for bit what they are.  The prefill's own attention reads the prompt's
+        unquantised K and V; only what it writes to the cache is quantised.  The result is that of a model whose K / V
+        rows pass through ``dequantize_rows(*quantize_rows_reference(row))`` when stored, which the CPU path computes
+        (its reference).  The default (None) is ``"bf16"``, or the storage of a passed ``cache``; an explicit value that
+        contradicts a passed ``cache`` is refused.  Independent of ``decode_weights`` and of every other argument.
 
         ``top_p`` (both samplers): nucleus sampling after top-k.  ``sampler="device"`` draws with the counter-based
         generator instead of ``generator``: step i of row b uses u(``seed``, i, b), and the token is the one defined in
@@ -370,14 +382,16 @@ class GPT2(nn.Module):
         return G.generate(self, idx, max_new_tokens, temperature=temperature, top_k=top_k, eos_token=eos_token,
                           prompt_lens=prompt_lens, generator=generator, graph=graph, return_logits=return_logits,
                           cache=cache, top_p=top_p, sampler=sampler, seed=seed, speculate=speculate, draft=draft,
-                          ngram=ngram, return_stats=return_stats, resume=resume, decode_weights=decode_weights)
+                          ngram=ngram, return_stats=return_stats, resume=resume, decode_weights=decode_weights,
+                          kv_cache=kv_cache)
 
-    def session(self, B, max_len, S=1, decode_weights="bf16"):
+    def session(self, B, max_len, S=1, decode_weights="bf16", kv_cache="bf16"):
         """A :class:`generation.Session`: B conversations of up to ``max_len`` tokens whose key/value cache is kept from
         one ``session.generate(turns, max_new_tokens, ...)`` to the next (``S``: the largest ``speculate`` to be used).
         ``decode_weights="fp8"`` (see :meth:`generate`) quantises once, here; every turn reuses that set, which is a
-        snapshot of the weights at this moment: a later update of the model does not reach it."""
-        return G.Session(self, B, max_len, S, decode_weights)
+        snapshot of the weights at this moment: a later update of the model does not reach it.  ``kv_cache="fp8"``: the
+        kept cache stores e4m3 codes (see :meth:`generate`)."""
+        return G.Session(self, B, max_len, S, decode_weights, kv_cache)
 
     def _forward_reference(self, idx, targets=None, doc=None, drop=None):
         B, T = idx.shape

@@ -157,6 +157,11 @@ _SIGS = {
     "pdnn_kv_cache_append": [P, P, P, P, I, I, I, I, P],
     "pdnn_attn_extend": [P, P, P, P, P, I, I, I, I, F, P],
     "pdnn_attn_extend_tile": [],
+    "pdnn_kv_cache_fill_fp8": [P, P, P, P, P, I, I, I, I, P],
+    "pdnn_kv_cache_append_fp8": [P, P, P, P, P, P, I, I, I, I, P],
+    "pdnn_attn_decode_fp8": [P, P, P, P, P, P, P, P, I, I, I, I, F, P],
+    "pdnn_attn_decode_multi_fp8": [P, P, P, P, P, P, P, P, I, I, I, I, I, F, P],
+    "pdnn_attn_extend_fp8": [P, P, P, P, P, P, P, I, I, I, I, F, P],
     "pdnn_dropout_add_fwd": [P, P, P, L, I, F, P, I, P],
     "pdnn_dropout_bwd": [P, P, L, I, F, P, I, P],
     "pdnn_dropout_mask_rows": [P, L, I, F, P, I, P],

@@ -1565,21 +1565,27 @@ DECODE_CHUNK = 128          # keys per block of the split; profiles/attention_de
 DECODE_CHUNKS = (64, 128, 256)
 
 
-def _cache_chk(name, kcache, vcache, dev):
+def _cache_chk(name, kcache, vcache, dev, scales=None):
+    """``scales`` = (kscale, vscale): the fp8 cache, uint8 codes with fp32 [B][H][Tmax] row scales"""
+    dtype, dname = (BF16, "bf16") if scales is None else (torch.uint8, "uint8")
     for t, what in ((kcache, "kcache"), (vcache, "vcache")):
-        _chk(torch.is_tensor(t) and t.dtype == BF16 and t.is_cuda and t.dim() == 4 and t.shape[3] == 64
+        _chk(torch.is_tensor(t) and t.dtype == dtype and t.is_cuda and t.dim() == 4 and t.shape[3] == 64
              and t.is_contiguous() and t.device == dev and t.data_ptr() % 16 == 0,
-             f"{name}: {what} must be contiguous CUDA bf16 [B][H][Tmax][64] on {dev}")
+             f"{name}: {what} must be contiguous CUDA {dname} [B][H][Tmax][64] on {dev}")
     _chk(kcache.shape == vcache.shape and min(kcache.shape) >= 1,
          f"{name}: kcache {tuple(kcache.shape)} and vcache {tuple(vcache.shape)} must have one non-empty shape")
+    for t, what in zip(scales or (), ("kscale", "vscale")):
+        _chk(torch.is_tensor(t) and t.dtype == F32 and t.shape == kcache.shape[:3] and t.is_contiguous() and t.device == dev,
+             f"{name}: {what} must be contiguous CUDA fp32 {tuple(kcache.shape[:3])} on {dev}")
 
 
-def _attn_decode(name, sym, S, qkv, kcache, vcache, lens, chunk, out, part, scale):
-    """The checks and the launch of :func:`attn_decode` (``S`` None: its C entry takes none) and :func:`attn_decode_multi`"""
+def _attn_decode(name, sym, S, qkv, kcache, vcache, lens, chunk, out, part, scale, scales=None):
+    """The checks and the launch of :func:`attn_decode` (``S`` None: its C entry takes none) and :func:`attn_decode_multi`,
+    and of their fp8-cache twins (``scales`` = (kscale, vscale))"""
     _bf16_c(qkv, f"{name}.qkv")
     _chk(isinstance(chunk, int) and chunk in DECODE_CHUNKS, f"{name}: chunk must be one of {DECODE_CHUNKS}, got {chunk!r}")
     _chk(S is None or (isinstance(S, int) and 1 <= S <= DECODE_MAX_S), f"{name}: 1 <= S <= {DECODE_MAX_S}, got S = {S!r}")
-    _cache_chk(name, kcache, vcache, qkv.device)
+    _cache_chk(name, kcache, vcache, qkv.device, scales)
     B, H, Tmax, _ = kcache.shape
     if S is None:
         R, per, want = B, (), f"B={B} H={H}: expected [B][3*H*64]"
@@ -1599,8 +1605,8 @@ def _attn_decode(name, sym, S, qkv, kcache, vcache, lens, chunk, out, part, scal
     else:
         _chk(part.dtype == F32 and part.is_contiguous() and part.numel() >= ws and part.device == qkv.device,
              f"{name}: part must be contiguous fp32 with >= {ws} elements on {qkv.device}")
-    call(sym, ptr(qkv), ptr(kcache), ptr(vcache), ptr(lens), ptr(out), ptr(part), B, *per, H, Tmax, chunk,
-         float(0.125 if scale is None else scale), stream())
+    call(sym, ptr(qkv), ptr(kcache), ptr(vcache), *map(ptr, scales or ()), ptr(lens), ptr(out), ptr(part), B, *per, H, Tmax,
+         chunk, float(0.125 if scale is None else scale), stream())
     return out
 
 
@@ -1709,10 +1715,10 @@ def kv_cache_fill(qkv, kcache, vcache, B, T):
 EXTEND_TILE = 64            # queries per block of attn_extend (pdnn_attn_extend_tile): Tq must be a multiple of it
 
 
-def _extend_chk(name, qkv, kcache, vcache, lens):
-    """-> (B, Tq, H, Tmax) of one kv_cache_append / attn_extend call"""
+def _extend_chk(name, qkv, kcache, vcache, lens, scales=None):
+    """-> (B, Tq, H, Tmax) of one kv_cache_append / attn_extend call (``scales``: their fp8-cache twins)"""
     _bf16_c(qkv, f"{name}.qkv")
-    _cache_chk(name, kcache, vcache, qkv.device)
+    _cache_chk(name, kcache, vcache, qkv.device, scales)
     B, H, Tmax, _ = kcache.shape
     _chk(qkv.dim() == 2 and qkv.shape[1] == 3 * H * 64 and qkv.shape[0] >= B and qkv.shape[0] % (B * EXTEND_TILE) == 0,
          f"{name}: qkv {tuple(qkv.shape)} for B={B} H={H}: expected [B*Tq][3*H*64] with Tq a multiple of {EXTEND_TILE}")
@@ -1742,6 +1748,57 @@ def attn_extend(qkv, kcache, vcache, lens, out=None, scale=None):
              f"attn_extend: out must be contiguous bf16 [{B * Tq}][{H * 64}] on {qkv.device}")
     call("pdnn_attn_extend", ptr(qkv), ptr(kcache), ptr(vcache), ptr(lens), ptr(out), B, Tq, H, Tmax,
          float(0.125 if scale is None else scale), stream())
+    return out
+
+
+# ----------------------------------------------------------------------------------- fp8 key/value cache (attention_cache_fp8.hip)
+# The cache of generate(kv_cache="fp8"): kcache / vcache uint8 [B][H][Tmax][64] e4m3fn codes, kscale / vscale fp32
+# [B][H][Tmax], one power-of-two scale per 64-element row by the rule of ops/quant.py.  Each wrapper is its bf16 twin's
+# contract with every key and value replaced by dequantize_rows(*quantize_rows_reference(row)).
+def kv_cache_fill_fp8(qkv, kcache, vcache, kscale, vscale, B, T):
+    """:func:`kv_cache_fill` into the fp8 cache: codes and scales of slots 0..T-1 equal quantize_rows_reference bitwise"""
+    _bf16_c(qkv, "kv_cache_fill_fp8.qkv")
+    _cache_chk("kv_cache_fill_fp8", kcache, vcache, qkv.device, (kscale, vscale))
+    Bc, H, Tmax, _ = kcache.shape
+    _chk(B == Bc and 1 <= T <= Tmax and qkv.shape == (B * T, 3 * H * 64),
+         f"kv_cache_fill_fp8: qkv {tuple(qkv.shape)} B={B} T={T} for a cache {tuple(kcache.shape)}")
+    call("pdnn_kv_cache_fill_fp8", ptr(qkv), ptr(kcache), ptr(vcache), ptr(kscale), ptr(vscale), B, T, H, Tmax, stream())
+
+
+def kv_cache_append_fp8(qkv, kcache, vcache, kscale, vscale, lens):
+    """:func:`kv_cache_append` into the fp8 cache (a slot >= Tmax is not stored, neither codes nor scale)"""
+    B, Tq, H, Tmax = _extend_chk("kv_cache_append_fp8", qkv, kcache, vcache, lens, (kscale, vscale))
+    call("pdnn_kv_cache_append_fp8", ptr(qkv), ptr(kcache), ptr(vcache), ptr(kscale), ptr(vscale), ptr(lens), B, Tq, H,
+         Tmax, stream())
+
+
+def attn_decode_fp8(qkv, kcache, vcache, kscale, vscale, lens, chunk=DECODE_CHUNK, out=None, part=None, scale=None):
+    """:func:`attn_decode` on the fp8 cache: the new k, v rows are quantised in the kernel, stored as codes and scale
+    into slot lens[b], and enter the softmax as their dequantised values, like every cached row.  ``part``: fp32, >=
+    attn_decode_ws elements."""
+    return _attn_decode("attn_decode_fp8", "pdnn_attn_decode_fp8", None, qkv, kcache, vcache, lens, chunk, out, part,
+                        scale, (kscale, vscale))
+
+
+def attn_decode_multi_fp8(qkv, kcache, vcache, kscale, vscale, lens, S, chunk=DECODE_CHUNK, out=None, part=None,
+                          scale=None):
+    """:func:`attn_decode_multi` on the fp8 cache: bit for bit what S successive :func:`attn_decode_fp8` calls give with
+    lens advanced by one between them, output, codes and scales.  ``part``: fp32, >= attn_decode_multi_ws elements."""
+    return _attn_decode("attn_decode_multi_fp8", "pdnn_attn_decode_multi_fp8", S, qkv, kcache, vcache, lens, chunk, out,
+                        part, scale, (kscale, vscale))
+
+
+def attn_extend_fp8(qkv, kcache, vcache, kscale, vscale, lens, out=None, scale=None):
+    """:func:`attn_extend` on the fp8 cache, after :func:`kv_cache_append_fp8` of the same qkv on the same stream: bit for
+    bit :func:`attn_extend` on the dequantised cache."""
+    B, Tq, H, Tmax = _extend_chk("attn_extend_fp8", qkv, kcache, vcache, lens, (kscale, vscale))
+    if out is None:
+        out = torch.empty(B * Tq, H * 64, device=qkv.device, dtype=BF16)
+    else:
+        _chk(out.dtype == BF16 and out.shape == (B * Tq, H * 64) and out.is_contiguous() and out.device == qkv.device,
+             f"attn_extend_fp8: out must be contiguous bf16 [{B * Tq}][{H * 64}] on {qkv.device}")
+    call("pdnn_attn_extend_fp8", ptr(qkv), ptr(kcache), ptr(vcache), ptr(kscale), ptr(vscale), ptr(lens), ptr(out), B, Tq,
+         H, Tmax, float(0.125 if scale is None else scale), stream())
     return out
 
 

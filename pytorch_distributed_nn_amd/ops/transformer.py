@@ -488,10 +488,14 @@ class KVCache:
     allocation bf16 [L][B][H][Tmax][64], ``lens`` int32 [B] on the device (tokens of sequence b already cached; the
     decode kernels read it there, the host never does) and the fp32 scratch of the split decode kernel, sized for ``S``
     queries per sequence (S > 1: :func:`block_step`).  Slots at or past lens[b] may hold anything, so :meth:`reset`
-    only zeroes ``lens``."""
+    only zeroes ``lens``.  ``dtype="fp8"`` (csrc/kernels/attention_cache_fp8.hip): ``k``, ``v`` are uint8 e4m3fn codes of
+    the same shape and ``ks``, ``vs`` fp32 [L][B][H][Tmax] the power-of-two scale of every 64-element row (ops/quant.py),
+    68 bytes per row instead of 128; the blocks below choose their kernels from ``dtype``."""
 
-    def __init__(self, model, B, Tmax, device, chunk=None, S=1):
+    def __init__(self, model, B, Tmax, device, chunk=None, S=1, dtype="bf16"):
         c = model.config
+        if dtype not in ("bf16", "fp8"):
+            raise ValueError(f"KVCache: dtype must be 'bf16' or 'fp8', got {dtype!r}")
         need_fused_kernels(c.n_embd, c.n_head)
         if B < 1 or Tmax < 1:
             raise ValueError(f"KVCache: B = {B}, Tmax = {Tmax}")
@@ -499,13 +503,21 @@ class KVCache:
             raise ValueError(f"KVCache: 1 <= S <= {K.DECODE_MAX_S}, got S = {S!r}")
         self.B, self.H, self.Tmax, self.L, self.S = B, c.n_head, Tmax, c.n_layer, S
         self.chunk = K.DECODE_CHUNK if chunk is None else chunk
-        self.k = torch.zeros(c.n_layer, B, c.n_head, Tmax, 64, device=device, dtype=BF16)
+        self.dtype = dtype
+        self.k = torch.zeros(c.n_layer, B, c.n_head, Tmax, 64, device=device, dtype=BF16 if dtype == "bf16" else torch.uint8)
         self.v = torch.zeros_like(self.k)
+        if dtype == "fp8":
+            self.ks = torch.ones(c.n_layer, B, c.n_head, Tmax, device=device, dtype=F32)
+            self.vs = torch.ones_like(self.ks)
         self.lens = torch.zeros(B, device=device, dtype=torch.int32)
         self.part = torch.empty(K.attn_decode_multi_ws(B, S, c.n_head, Tmax, self.chunk), device=device, dtype=F32)
 
     def reset(self):
         self.lens.zero_()
+
+    def layer(self, i):
+        """The cache tensors of layer ``i`` as the attention kernels take them: (k, v), or (k, v, ks, vs) of an fp8 cache"""
+        return (self.k[i], self.v[i]) if self.dtype == "bf16" else (self.k[i], self.v[i], self.ks[i], self.vs[i])
 
     def truncate(self, lens):
         """Rewind: lens[b] = min(lens[b], ``lens``[b]) on the device (``lens``: an int, or B of them).  Slots past lens
@@ -545,8 +557,10 @@ def block_prefill(x, conf, shadows, params, cache, layer):
     B, T, H, eps = conf[:4]
     need_fused_kernels(x.shape[1], H, T)
 
-    def attn(qkv):      # a prompt is one document, and nothing is dropped
-        K.kv_cache_fill(qkv, cache.k[layer], cache.v[layer], B, T)
+    fill = K.kv_cache_fill if cache.dtype == "bf16" else K.kv_cache_fill_fp8
+
+    def attn(qkv):      # a prompt is one document, and nothing is dropped; it attends to its own unquantised K and V
+        fill(qkv, *cache.layer(layer), B, T)
         return K.flash_attn_fwd(qkv, B, T, H, 1.0 / math.sqrt(x.shape[1] // H))[0]
     return _block_infer(x, eps, shadows, params, BL.linear_fwd, attn)
 
@@ -557,18 +571,19 @@ def block_step(x, conf, shadows, params, cache, layer, S=1):
     BL.linear_fwd_decode and K.attn_decode.  S > 1, a speculative verify step: K.attn_decode_multi, and K.gemm_skinny
     for every M = B*S <= K.SKINNY_ROWS, whose row bits do not depend on M: a row gets the bits of the S == 1 step.
     ``shadows`` of pairs (q, inv) (ops/quant.py) run the four linears on K.gemm_skinny_fp8 for S == 1 and S > 1 alike: the
-    same kernel, row bits independent of M."""
+    same kernel, row bits independent of M.  An fp8 ``cache`` runs K.attn_decode_fp8 / K.attn_decode_multi_fp8."""
     B, _, H, eps = conf[:4]
+    fp8 = cache.dtype == "fp8"
     if S == 1:
-        lin, attn, multi = BL.linear_fwd_decode, K.attn_decode, {}
+        lin, attn, multi = BL.linear_fwd_decode, K.attn_decode_fp8 if fp8 else K.attn_decode, {}
     else:
         if S > cache.S or x.shape[0] != B * S or x.shape[0] > K.SKINNY_ROWS:    # (the text of block_verify, now this S > 1)
             raise ValueError(f"block_verify: {x.shape[0]} rows for B = {B}, S = {S} (cache S = {cache.S}, at most "
                              f"{K.SKINNY_ROWS} rows)")
-        lin, attn, multi = K.gemm_skinny, K.attn_decode_multi, {"S": S}
+        lin, attn, multi = K.gemm_skinny, K.attn_decode_multi_fp8 if fp8 else K.attn_decode_multi, {"S": S}
     if isinstance(shadows[0], tuple):       # fp8 decode weights, pairs (q, inv): one kernel for every row count
         lin = BL.linear_fwd_decode
-    return _block_infer(x, eps, shadows, params, lin, attn, cache.k[layer], cache.v[layer], cache.lens, chunk=cache.chunk,
+    return _block_infer(x, eps, shadows, params, lin, attn, *cache.layer(layer), cache.lens, chunk=cache.chunk,
                         part=cache.part, scale=1.0 / math.sqrt(x.shape[1] // H), **multi)
 
 
@@ -583,9 +598,12 @@ def block_extend(x, conf, shadows, params, cache, layer):
         raise ValueError(f"block_extend: {x.shape[0]} rows for B = {B}, Tq = {Tq} (a multiple of {K.EXTEND_TILE}), cache "
                          f"B = {cache.B}")
 
+    append, extend = (K.kv_cache_append, K.attn_extend) if cache.dtype == "bf16" else (K.kv_cache_append_fp8,
+                                                                                        K.attn_extend_fp8)
+
     def attn(qkv):
-        K.kv_cache_append(qkv, cache.k[layer], cache.v[layer], cache.lens)
-        return K.attn_extend(qkv, cache.k[layer], cache.v[layer], cache.lens, scale=1.0 / math.sqrt(x.shape[1] // H))
+        append(qkv, *cache.layer(layer), cache.lens)
+        return extend(qkv, *cache.layer(layer), cache.lens, scale=1.0 / math.sqrt(x.shape[1] // H))
     return _block_infer(x, eps, shadows, params, BL.linear_fwd, attn)
 
 

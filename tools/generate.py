@@ -63,6 +63,8 @@ def build_parser():
     ap.add_argument("--decode-weights", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: the decode steps stream the block linears and the LM head as e4m3 codes with row scales "
                          "(weight-only; GPT2.generate)")
+    ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: the key/value cache holds e4m3 codes with one scale per 64-element row (GPT2.generate)")
     return ap
 
 
@@ -95,13 +97,15 @@ def main(argv=None):
     if args.chunk is not None and args.chunk < 1:
         raise SystemExit(f"--chunk {args.chunk}: expected a positive number of tokens")
     kw = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, eos_token=args.eos_token,
-              graph=args.graph and dev.type == "cuda", decode_weights=args.decode_weights, **draw)
+              graph=args.graph and dev.type == "cuda", decode_weights=args.decode_weights, kv_cache=args.kv_cache,
+              **draw)
     idx = idx.to(dev)
     try:
         if args.chunk is not None and dev.type == "cuda":
             from pytorch_distributed_nn_amd.ops.transformer import KVCache
             S = args.speculate or 1
-            cache = KVCache(model, idx.shape[0], idx.shape[1] + args.max_new_tokens + (S if S > 1 else 0), dev, S=S)
+            cache = KVCache(model, idx.shape[0], idx.shape[1] + args.max_new_tokens + (S if S > 1 else 0), dev, S=S,
+                            dtype=args.kv_cache)
             pieces = list(idx.split(args.chunk, dim=1))
             for piece in pieces[:-1]:
                 model.generate(piece, 0, cache=cache, resume=True)
