@@ -39,9 +39,9 @@ def sample(logits, temperature, top_k, generator, top_p=None):
 
 # one checked call: N = max_new_tokens, pl = the B prompt lengths, draw = dict(temperature, top_k, top_p), seed masked to
 # 63 bits (sampler="device", else None), S = speculate or None, guess = the draft table or None (n-gram drafts), kv = the
-# cache's storage, "bf16" or "fp8"
+# cache's storage, "bf16" or "fp8", fused = decode_fused
 Request = namedtuple("Request", "B P N pl draw eos generator seed S guess ngram graph return_logits return_stats cache "
-                     "resume decode_weights kv", defaults=(False, "bf16", "bf16"))
+                     "resume decode_weights kv fused", defaults=(False, "bf16", "bf16", False))
 
 
 class DecodeWeights:
@@ -70,7 +70,7 @@ class DecodeWeights:
 
 def check_args(c, idx, max_new_tokens, *, temperature, top_k, eos_token, prompt_lens, generator, graph,
                return_logits, cache, top_p, sampler, seed, speculate, draft, ngram, return_stats, resume=False,
-               decode_weights="bf16", kv_cache=None):
+               decode_weights="bf16", kv_cache=None, decode_fused=False):
     """``generate``'s arguments and the model's config ``c`` -> :class:`Request`, or the first refusal in this order"""
     if idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
         raise ValueError(f"generate: idx must be [B][P] with B, P >= 1, got {tuple(idx.shape)}")
@@ -136,9 +136,16 @@ def check_args(c, idx, max_new_tokens, *, temperature, top_k, eos_token, prompt_
     have = getattr(cache, "dtype", None)                # None: the cache follows a passed cache=, else it is bf16
     if kv_cache is not None and have is not None and have != kv_cache:
         raise ValueError(f"generate: kv_cache={kv_cache!r} with a cache= of dtype {have!r}")
+    if decode_fused and idx.is_cuda and (not tuning.get("decode_skinny") or B * (S or 1) > K.FUSED_ROWS
+                                         or c.n_embd % 8 or c.n_embd > K.FUSED_MAX_D):
+        raise ValueError(f"generate: decode_fused on the GPU needs tuning decode_skinny on, B * speculate <= "
+                         f"{K.FUSED_ROWS} (the prologue kernels take one 16-row tile) and n_embd % 8 == 0, n_embd <= "
+                         f"{K.FUSED_MAX_D}; got decode_skinny = {tuning.get('decode_skinny')!r}, B = {B}, S = {S}, "
+                         f"n_embd = {c.n_embd}")
     return Request(B, P, max_new_tokens, pl, dict(temperature=float(temperature), top_k=top_k, top_p=top_p), eos_token,
                    generator, int(seed) & ((1 << 63) - 1) if sampler == "device" else None, S, guess, ngram, graph,
-                   return_logits, return_stats, cache, bool(resume), decode_weights, kv_cache or have or "bf16")
+                   return_logits, return_stats, cache, bool(resume), decode_weights, kv_cache or have or "bf16",
+                   bool(decode_fused))
 
 
 def check_resume(c, idx, B, pl, N, S, cache):
@@ -182,9 +189,10 @@ class Engine:
     """One call's GPU model: the cache (``cache`` if it fits, reset; else a new one), bf16 shadows, block parameters.
     ``dec`` (a :class:`DecodeWeights`): ``rows`` and every LM-head GEMM run on its fp8 pairs; prefill and extend blocks
     keep the bf16 shadows.  ``kv``: the storage of a new cache (check_args has held a passed one against it); the blocks
-    take their attention kernels from the cache."""
+    take their attention kernels from the cache.  ``fused`` (``decode_fused``): ``rows`` runs TX.block_step(fused=True);
+    ln_f and the LM head stay two launches (fused, the 3144-block head lost: profiles/decode_fused.txt)."""
 
-    def __init__(self, model, B, P, N, S=1, cache=None, resume=False, dec=None, kv="bf16"):
+    def __init__(self, model, B, P, N, S=1, cache=None, resume=False, dec=None, kv="bf16", fused=False):
         self.config, tr = model.config, model.transformer
         dev = tr.wte.weight.device
         Tneed = model.kv_cache_len(P, N + (S if S > 1 else 0))       # rejected drafts occupy slots past the accepted length
@@ -199,7 +207,7 @@ class Engine:
             raise ValueError(f"generate: kv_cache={kv!r} with a cache of dtype {cache.dtype!r}")
         if not resume:
             cache.reset()
-        self.B, self.cache = B, cache
+        self.B, self.cache, self.fused = B, cache, fused
         self.wte_k, self.wpe_k = OF.weight_bf16(tr.wte.weight), OF.weight_bf16(tr.wpe.weight)
         self.blocks = [blk.fused_params() for blk in tr.h]
         self.lnw, self.lnb = tr.ln_f.weight, tr.ln_f.bias
@@ -251,7 +259,7 @@ class Engine:
         conf = (self.B, S, c.n_head, c.eps)
         x = K.embedding_decode(tok, pos, self.wte_k, self.wpe_k)
         for layer, (params, shadows) in enumerate(self.step_blocks):
-            x = TX.block_step(x, conf, shadows, params, self.cache, layer, S)
+            x = TX.block_step(x, conf, shadows, params, self.cache, layer, S, self.fused)
         xf, _, _ = K.layernorm_fwd(x, self.lnw, self.lnb, c.eps)
         if S == 1 or self.head is not self.wte_k:
             return BL.linear_fwd_decode(xf, self.head)
@@ -310,11 +318,12 @@ class Reference:
         return F.linear(tr.ln_f(x), self.head).float()
 
 
-def fused_stepper(model, idx, pl_dev, max_new_tokens, graph=False, cache=None, resume=False, dec=None, kv="bf16"):
+def fused_stepper(model, idx, pl_dev, max_new_tokens, graph=False, cache=None, resume=False, dec=None, kv="bf16",
+                  fused=False):
     """GPU: prefill -> (fp32 logits [B][V] at each prompt's last position, step(tok) -> the next logits, in one fp32
     buffer).  The engine of the torch-sampler loop: the token comes from the host side of the loop."""
     B, P = idx.shape
-    eng = Engine(model, B, P, max_new_tokens, 1, cache, resume, dec, kv)
+    eng = Engine(model, B, P, max_new_tokens, 1, cache, resume, dec, kv, fused)
     logits16 = eng.ingest(idx, pl_dev, resume)
     tok_buf = torch.zeros(B, dtype=torch.int64, device=idx.device)
     logits = logits16.float()
@@ -436,7 +445,7 @@ def generate(model, idx, max_new_tokens, **kw):
     if r.guess is not None:
         r = r._replace(guess=r.guess.to(idx.device).contiguous())
     if r.seed is not None and idx.is_cuda:         # the sampling kernel is inside the step: the loop is on the device
-        eng = Engine(model, B, P, N, r.S or 1, r.cache, r.resume, dec, r.kv)
+        eng = Engine(model, B, P, N, r.S or 1, r.cache, r.resume, dec, r.kv, r.fused)
         logit_buf = eng.ingest(idx, pl_dev, r.resume)
         res = _speculate_device(eng, r, pl_dev, out, logit_buf) if r.S else _device_loop(eng, r, out, logit_buf)
         return (out, res) if r.return_logits or r.return_stats else out
@@ -445,7 +454,7 @@ def generate(model, idx, max_new_tokens, **kw):
         return (out, stats) if r.return_stats else out
     # the token is drawn on the host side of the loop: the torch sampler on both devices, the device sampler's reference
     if idx.is_cuda:
-        logits, step = fused_stepper(model, idx, pl_dev, N, r.graph, r.cache, r.resume, dec, r.kv)
+        logits, step = fused_stepper(model, idx, pl_dev, N, r.graph, r.cache, r.resume, dec, r.kv, r.fused)
     else:
         ref = Reference(model, B, max(r.pl) + N, dec, r.kv)
         logits, step = ref.prefill(idx, pl_dev), ref.step
@@ -481,7 +490,7 @@ class Session:
     it: a turn costs its own tokens against the cache, not the whole history again.  On the CPU there is no cache: the
     same call re-runs ``generate`` on the concatenated history, which is the definition the GPU path is held to."""
 
-    def __init__(self, model, B, max_len, S=1, decode_weights="bf16", kv_cache="bf16"):
+    def __init__(self, model, B, max_len, S=1, decode_weights="bf16", kv_cache="bf16", decode_fused=False):
         if decode_weights not in ("bf16", "fp8") or kv_cache not in ("bf16", "fp8"):
             raise ValueError(f"session: decode_weights and kv_cache must be 'bf16' or 'fp8', got {decode_weights!r}, "
                              f"{kv_cache!r}")
@@ -495,6 +504,7 @@ class Session:
         # quantised once, here: every turn runs on this snapshot of the weights
         self.sampling = {"decode_weights": DecodeWeights(model)} if decode_weights == "fp8" else {}
         self.sampling["kv_cache"] = kv_cache
+        self.sampling["decode_fused"] = bool(decode_fused)
 
     def generate(self, turns, max_new_tokens, *, eos_token=None, **sampling):
         """``turns``: B token sequences (lists or 1-D tensors), row b's next turn; it may be empty only where the row has

@@ -304,7 +304,7 @@ class GPT2(nn.Module):
     def generate(self, idx, max_new_tokens, *, temperature=1.0, top_k=None, eos_token=None, prompt_lens=None,
                  generator=None, graph=False, return_logits=False, cache=None, top_p=None, sampler="torch", seed=None,
                  speculate=None, draft="ngram", ngram=3, return_stats=False, resume=False, decode_weights="bf16",
-                 kv_cache=None):
+                 kv_cache=None, decode_fused=False):
         """Sample ``max_new_tokens`` tokens after the prompts ``idx`` int [B][P] with a key/value cache: one prefill over
         the prompt, then one single-token step per new token (GPU: ``ops.transformer.block_step`` on the decode
         attention kernel of ``csrc/kernels/attention_decode.hip``; CPU: plain PyTorch in fp32 with per-layer k, v lists,
@@ -348,6 +348,15 @@ class GPT2(nn.Module):
         (its reference).  The default (None) is ``"bf16"``, or the storage of a passed ``cache``; an explicit value that
         contradicts a passed ``cache`` is refused.  Independent of ``decode_weights`` and of every other argument.
 
+        ``decode_fused=True`` (GPU; off by default): every decode and verify step runs six launches per block instead
+        of eight.  LN1 and LN2 become prologues of the qkv and fc GEMMs (``ops.kernels.gemm_skinny_ln``, the kernel of
+        ``csrc/kernels/gemm_skinny_pro.hip``: each block normalises the few rows into LDS and then streams its weights as
+        the skinny GEMMs do), for both weight formats and both cache dtypes.  The GEMM part has the bits of the unfused
+        kernels; the LayerNorm prologue is a two-pass fp32 LayerNorm of its own, so tokens may differ from
+        ``decode_fused=False`` where two logits are within a bf16 rounding.  Row bits do not depend on the row count:
+        speculation, graph replay and resume stay bit for bit what they are with it.  The GPU path needs tuning
+        ``decode_skinny`` and B * (speculate or 1) <= 16.  The CPU path accepts the option and is unchanged.
+
         ``top_p`` (both samplers): nucleus sampling after top-k.  ``sampler="device"`` draws with the counter-based
         generator instead of ``generator``: step i of row b uses u(``seed``, i, b), and the token is the one defined in
         the header of ``csrc/kernels/sample.hip`` (GPU: that kernel, on the step's bf16 logits, writing the token, the
@@ -383,15 +392,16 @@ class GPT2(nn.Module):
                           prompt_lens=prompt_lens, generator=generator, graph=graph, return_logits=return_logits,
                           cache=cache, top_p=top_p, sampler=sampler, seed=seed, speculate=speculate, draft=draft,
                           ngram=ngram, return_stats=return_stats, resume=resume, decode_weights=decode_weights,
-                          kv_cache=kv_cache)
+                          kv_cache=kv_cache, decode_fused=decode_fused)
 
-    def session(self, B, max_len, S=1, decode_weights="bf16", kv_cache="bf16"):
+    def session(self, B, max_len, S=1, decode_weights="bf16", kv_cache="bf16", decode_fused=False):
         """A :class:`generation.Session`: B conversations of up to ``max_len`` tokens whose key/value cache is kept from
         one ``session.generate(turns, max_new_tokens, ...)`` to the next (``S``: the largest ``speculate`` to be used).
         ``decode_weights="fp8"`` (see :meth:`generate`) quantises once, here; every turn reuses that set, which is a
         snapshot of the weights at this moment: a later update of the model does not reach it.  ``kv_cache="fp8"``: the
-        kept cache stores e4m3 codes (see :meth:`generate`)."""
-        return G.Session(self, B, max_len, S, decode_weights, kv_cache)
+        kept cache stores e4m3 codes (see :meth:`generate`).  ``decode_fused``: every turn's steps run the fused
+        sequence (see :meth:`generate`)."""
+        return G.Session(self, B, max_len, S, decode_weights, kv_cache, decode_fused)
 
     def _forward_reference(self, idx, targets=None, doc=None, drop=None):
         B, T = idx.shape

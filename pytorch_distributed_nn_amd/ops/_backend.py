@@ -139,6 +139,8 @@ _SIGS = {
     "pdnn_quant_rows_e4m3": [P, I, I, P, P, P],
     "pdnn_gemm_skinny_fp8": [P, L, P, P, P, L, I, I, I, P, I, P, P],
     "pdnn_gemm_skinny_fp8_plan": [I, I],
+    "pdnn_gemm_skinny_ln": [P, L, P, P, F, P, P, L, I, I, I, P, I, P, P],
+    "pdnn_gemm_skinny_ln_fp8": [P, L, P, P, F, P, P, P, L, I, I, I, P, I, P, P],
     "pdnn_layernorm_fwd": [P, P, P, P, P, P, I, I, F, P],
     "pdnn_layernorm_bwd_blocks": [I],
     "pdnn_layernorm_bwd": [P, P, P, P, P, P, P, P, I, I, I, P],

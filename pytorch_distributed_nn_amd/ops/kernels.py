@@ -1432,6 +1432,52 @@ def gemm_skinny_fp8(x, q, inv, bias=None, act=0, res=None, out=None):
     return out
 
 
+FUSED_ROWS = 16             # rows the prologue kernel of csrc/kernels/gemm_skinny_pro.hip takes: one MFMA tile
+FUSED_MAX_D = 2048          # and its reduction length, the model width: layernorm_fwd's own limit
+
+
+def gemm_skinny_ln(x, gamma, beta, eps, w, bias=None, act=0, out=None, image=None):
+    """y = act(LayerNorm(x; gamma, beta, eps) @ w^T + bias) in one launch (csrc/kernels/gemm_skinny_pro.hip): every block
+    normalises the M <= FUSED_ROWS rows into LDS and streams its weight rows as :func:`gemm_skinny` /
+    :func:`gemm_skinny_fp8` do.  x bf16 [M][D] (row-strided), gamma / beta fp32 [D], D <= 2048; ``w`` a bf16 [N][D] tensor
+    or a pair (q uint8 [N][D], inv fp32 [N]) (D % 16 == 0); bias, act, out as there.  ``image``: bf16 [M][D] that also
+    receives the normalised rows; the result has the bits of the unfused GEMM on that image.  A row's bits do not depend
+    on M or on the other rows."""
+    _chk(torch.is_tensor(x) and x.dtype == BF16 and x.is_cuda and x.dim() == 2 and x.data_ptr() % 16 == 0,
+         "gemm_skinny_ln: x must be a 16-byte aligned 2-D CUDA bf16 tensor")
+    M, D = x.shape
+    dev = x.device
+    fp8 = isinstance(w, tuple)
+    wt, dt, dq = (w[0], torch.uint8, 16) if fp8 else (w, BF16, 8)
+    _chk(1 <= M <= FUSED_ROWS, f"gemm_skinny_ln: 1 <= M <= {FUSED_ROWS}, got M = {M}")
+    _chk(dq <= D <= FUSED_MAX_D and D % dq == 0, f"gemm_skinny_ln: D % {dq} == 0 and D <= {FUSED_MAX_D}, got D = {D}")
+    _chk(x.stride(1) == 1 and x.stride(0) >= D and x.stride(0) % 8 == 0, "gemm_skinny_ln: x rows contiguous, row stride % 8 == 0")
+    for t, nm in ((gamma, "gamma"), (beta, "beta")):
+        _chk(torch.is_tensor(t) and t.dtype == F32 and t.shape == (D,) and t.is_contiguous() and t.device == dev,
+             f"gemm_skinny_ln: {nm} must be contiguous fp32 [{D}]")
+    _chk(torch.is_tensor(wt) and wt.dtype == dt and wt.dim() == 2 and wt.device == dev and wt.is_contiguous()
+         and wt.data_ptr() % 16 == 0 and wt.shape[1] == D and wt.shape[0] >= 8 and wt.shape[0] % 8 == 0,
+         f"gemm_skinny_ln: w must be a contiguous 16-byte aligned {dt} [N][{D}] on {dev}, N % 8 == 0")
+    N = wt.shape[0]
+    if fp8:
+        _chk(torch.is_tensor(w[1]) and w[1].dtype == F32 and w[1].shape == (N,) and w[1].is_contiguous()
+             and w[1].device == dev, f"gemm_skinny_ln: inv must be contiguous fp32 [{N}]")
+    _chk(act in (0, 2), f"gemm_skinny_ln: act must be 0 or 2 (GELU), got {act!r}")
+    _chk(bias is None or (bias.dtype == F32 and bias.shape == (N,) and bias.is_contiguous() and bias.device == dev),
+         f"gemm_skinny_ln: bias must be contiguous fp32 [{N}]")
+    if out is None:
+        out = torch.empty(M, N, device=dev, dtype=BF16)
+    _chk(out.dtype == BF16 and out.shape == (M, N) and out.device == dev and out.stride(1) == 1
+         and out.stride(0) >= N and out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0,
+         f"gemm_skinny_ln: out must be bf16 [{M}][{N}], rows contiguous, row stride % 8 == 0")
+    _chk(image is None or (image.dtype == BF16 and image.shape == (M, D) and image.is_contiguous() and image.device == dev
+                           and image.data_ptr() % 16 == 0), f"gemm_skinny_ln: image must be contiguous bf16 [{M}][{D}]")
+    wp = (ptr(w[0]), ptr(w[1])) if fp8 else (ptr(w),)
+    call("pdnn_gemm_skinny_ln_fp8" if fp8 else "pdnn_gemm_skinny_ln", ptr(x), x.stride(0), ptr(gamma), ptr(beta), float(eps),
+         *wp, ptr(out), out.stride(0), M, N, D, ptr(bias), int(act), ptr(image), stream())
+    return out
+
+
 def layernorm_fwd(x, g, b, eps):
     _bf16_c(x, "layernorm.x")
     _chk(x.dim() == 2, "layernorm: x must be 2-D")

@@ -565,15 +565,31 @@ def block_prefill(x, conf, shadows, params, cache, layer):
     return _block_infer(x, eps, shadows, params, BL.linear_fwd, attn)
 
 
-def block_step(x, conf, shadows, params, cache, layer, S=1):
+def _block_step_fused(x, eps, shadows, params, lin, attn, *args, **kw):
+    """:func:`block_step` with ``fused=True``: the step's own six launches.  LN1 and LN2 are prologues of the qkv and fc
+    GEMMs (K.gemm_skinny_ln); attention, proj and fc2 are those of the unfused step (``attn``, ``lin``).  The combine of
+    the decode attention as a prologue of proj lost at B = 8 and is not here (profiles/decode_fused.txt)."""
+    ln1w, ln1b, _, attn_b, _, proj_b, ln2w, ln2b, _, fc_b, _, fc2_b = params
+    wqkv, wproj, wfc, wfc2 = shadows
+    y = attn(K.gemm_skinny_ln(x, ln1w, ln1b, eps, wqkv, bias=attn_b), *args, **kw)
+    x1 = lin(y, wproj, bias=proj_b, res=x)
+    h = K.gemm_skinny_ln(x1, ln2w, ln2b, eps, wfc, bias=fc_b, act=2)
+    return lin(h, wfc2, bias=fc2_b, res=x1)
+
+
+def block_step(x, conf, shadows, params, cache, layer, S=1, fused=False):
     """One block on the S new tokens per sequence: x bf16 [B*S][D] -> x2, row b*S + j at position cache.lens[b] + j; the
     decode attention also stores the new k, v rows.  No host read-back; cache.lens unchanged.  S == 1, a decode step:
     BL.linear_fwd_decode and K.attn_decode.  S > 1, a speculative verify step: K.attn_decode_multi, and K.gemm_skinny
     for every M = B*S <= K.SKINNY_ROWS, whose row bits do not depend on M: a row gets the bits of the S == 1 step.
     ``shadows`` of pairs (q, inv) (ops/quant.py) run the four linears on K.gemm_skinny_fp8 for S == 1 and S > 1 alike: the
-    same kernel, row bits independent of M.  An fp8 ``cache`` runs K.attn_decode_fp8 / K.attn_decode_multi_fp8."""
+    same kernel, row bits independent of M.  An fp8 ``cache`` runs K.attn_decode_fp8 / K.attn_decode_multi_fp8.
+    ``fused=True`` (at most K.FUSED_ROWS rows): :func:`_block_step_fused`, six launches instead of eight, for every S,
+    weight format and cache dtype; its row bits do not depend on the row count either."""
     B, _, H, eps = conf[:4]
     fp8 = cache.dtype == "fp8"
+    if fused and x.shape[0] > K.FUSED_ROWS:
+        raise ValueError(f"block_step: fused=True takes at most {K.FUSED_ROWS} rows, got {x.shape[0]} (B = {B}, S = {S})")
     if S == 1:
         lin, attn, multi = BL.linear_fwd_decode, K.attn_decode_fp8 if fp8 else K.attn_decode, {}
     else:
@@ -583,7 +599,8 @@ def block_step(x, conf, shadows, params, cache, layer, S=1):
         lin, attn, multi = K.gemm_skinny, K.attn_decode_multi_fp8 if fp8 else K.attn_decode_multi, {"S": S}
     if isinstance(shadows[0], tuple):       # fp8 decode weights, pairs (q, inv): one kernel for every row count
         lin = BL.linear_fwd_decode
-    return _block_infer(x, eps, shadows, params, lin, attn, *cache.layer(layer), cache.lens, chunk=cache.chunk,
+    step = _block_step_fused if fused else _block_infer
+    return step(x, eps, shadows, params, lin, attn, *cache.layer(layer), cache.lens, chunk=cache.chunk,
                         part=cache.part, scale=1.0 / math.sqrt(x.shape[1] // H), **multi)
 
 

@@ -65,6 +65,9 @@ def build_parser():
                          "(weight-only; GPT2.generate)")
     ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: the key/value cache holds e4m3 codes with one scale per 64-element row (GPT2.generate)")
+    ap.add_argument("--decode-fused", action="store_true",
+                    help="GPU: LN1 and LN2 run as prologues of the qkv and fc GEMMs, six launches per block and step "
+                         "instead of eight (B * speculate <= 16; GPT2.generate)")
     return ap
 
 
@@ -98,7 +101,7 @@ def main(argv=None):
         raise SystemExit(f"--chunk {args.chunk}: expected a positive number of tokens")
     kw = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, eos_token=args.eos_token,
               graph=args.graph and dev.type == "cuda", decode_weights=args.decode_weights, kv_cache=args.kv_cache,
-              **draw)
+              decode_fused=args.decode_fused, **draw)
     idx = idx.to(dev)
     try:
         if args.chunk is not None and dev.type == "cuda":
