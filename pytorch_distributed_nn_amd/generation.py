@@ -15,7 +15,8 @@ from .ops import functional as OF
 from .ops import kernels as K
 from .ops import linear as BL
 from .ops import transformer as TX
-from .ops.quant import dequantize_rows, quantize_rows_reference
+from .ops.quant import (Fp8Rows, Mxfp4Blocks, dequantize_blocks, dequantize_rows, quantize_blocks_reference,
+                        quantize_rows_reference)
 from .ops.sampling import sample_reference
 from .ops.speculate import accept_reference, prepare_reference
 
@@ -44,28 +45,41 @@ Request = namedtuple("Request", "B P N pl draw eos generator seed S guess ngram 
                      "resume decode_weights kv fused", defaults=(False, "bf16", "bf16", False))
 
 
-class DecodeWeights:
-    """The fp8 decode weights of a model (``decode_weights="fp8"``): the four linears of every block and the tied LM
-    head as pairs (q e4m3fn codes, inv fp32 row scales) in the format of ops/quant.py, quantised from the bf16 weights
-    when this is made (GPU: K.quant_rows_e4m3; CPU: quantize_rows_reference).  A snapshot: later updates of the model's
-    weights do not reach it."""
+DECODE_WEIGHTS = ("bf16", "fp8", "mxfp4")
 
-    def __init__(self, model):
+
+class DecodeWeights:
+    """The quantised decode weights of a model: the four linears of every block and the tied LM head in the format
+    ``fmt`` of ops/quant.py, quantised from the bf16 weights when this is made.  ``"fp8"`` (``decode_weights="fp8"``):
+    Fp8Rows (q e4m3fn codes, inv fp32 row scales; GPU: K.quant_rows_e4m3, CPU: quantize_rows_reference).  ``"mxfp4"``:
+    Mxfp4Blocks (q e2m1 codes, sc e8m0 scales of 32-element blocks; GPU: K.quant_blocks_mxfp4, CPU:
+    quantize_blocks_reference).  A snapshot: later updates of the model's weights do not reach it."""
+
+    def __init__(self, model, fmt="fp8"):
+        if fmt not in ("fp8", "mxfp4"):
+            raise ValueError(f"DecodeWeights: fmt must be 'fp8' or 'mxfp4', got {fmt!r}")
         tr = model.transformer
+        self.fmt = fmt
+        form, on_gpu, on_cpu = (Fp8Rows, K.quant_rows_e4m3, quantize_rows_reference) if fmt == "fp8" else \
+            (Mxfp4Blocks, K.quant_blocks_mxfp4, quantize_blocks_reference)
         if tr.wte.weight.is_cuda:
-            quant = lambda w: K.quant_rows_e4m3(OF.weight_bf16(w))                          # noqa: E731
+            quant = lambda w: form(*on_gpu(OF.weight_bf16(w)))                               # noqa: E731
         else:
-            quant = lambda w: quantize_rows_reference(w.detach().to(torch.bfloat16))         # noqa: E731
+            quant = lambda w: form(*on_cpu(w.detach().to(torch.bfloat16)))                   # noqa: E731
         self.blocks = [tuple(quant(w) for w in (blk.attn.c_attn.weight, blk.attn.c_proj.weight, blk.mlp.c_fc.weight,
                                                 blk.mlp.c_proj.weight)) for blk in tr.h]
         self.wte = quant(tr.wte.weight)
 
     @staticmethod
     def of(model, decode_weights):
-        """generate's argument -> None ("bf16"), a new snapshot ("fp8") or the given one"""
+        """generate's argument -> None ("bf16"), a new snapshot ("fp8", "mxfp4") or the given one"""
         if isinstance(decode_weights, DecodeWeights):
             return decode_weights
-        return DecodeWeights(model) if decode_weights == "fp8" else None
+        return DecodeWeights(model, decode_weights) if decode_weights != "bf16" else None
+
+    def dequantize(self, w, dtype):
+        """one stored weight -> dq, exact in bf16"""
+        return (dequantize_rows if self.fmt == "fp8" else dequantize_blocks)(*w, dtype=dtype)
 
 
 def check_args(c, idx, max_new_tokens, *, temperature, top_k, eos_token, prompt_lens, generator, graph,
@@ -124,13 +138,19 @@ def check_args(c, idx, max_new_tokens, *, temperature, top_k, eos_token, prompt_
         TX.need_fused_kernels(c.n_embd, c.n_head)
     if resume:
         check_resume(c, idx, B, pl, max_new_tokens, S, cache)
-    if not (isinstance(decode_weights, DecodeWeights) or decode_weights in ("bf16", "fp8")):
-        raise ValueError(f"generate: decode_weights must be 'bf16' or 'fp8', got {decode_weights!r}")
-    if decode_weights != "bf16" and idx.is_cuda and (not tuning.get("decode_skinny") or B * (S or 1) > K.SKINNY_ROWS
-                                                      or c.n_embd % 16):
-        raise ValueError(f"generate: decode_weights='fp8' on the GPU needs tuning decode_skinny on, B * speculate <= "
-                         f"{K.SKINNY_ROWS} (the fp8 weights have the skinny kernel only) and n_embd % 16 == 0; got "
+    if not (isinstance(decode_weights, DecodeWeights) or (isinstance(decode_weights, str) and decode_weights in DECODE_WEIGHTS)):
+        raise ValueError(f"generate: decode_weights must be 'bf16', 'fp8' or 'mxfp4', got {decode_weights!r}")
+    fmt = decode_weights.fmt if isinstance(decode_weights, DecodeWeights) else decode_weights
+    if fmt == "mxfp4" and c.n_embd % 32:
+        raise ValueError(f"generate: decode_weights='mxfp4' needs n_embd % 32 == 0 (one scale per 32 reduction elements), "
+                         f"got n_embd = {c.n_embd}")
+    if fmt != "bf16" and idx.is_cuda and (not tuning.get("decode_skinny") or B * (S or 1) > K.SKINNY_ROWS or c.n_embd % 16):
+        raise ValueError(f"generate: decode_weights={fmt!r} on the GPU needs tuning decode_skinny on, B * speculate <= "
+                         f"{K.SKINNY_ROWS} (the {fmt} weights have the skinny kernel only) and n_embd % 16 == 0; got "
                          f"decode_skinny = {tuning.get('decode_skinny')!r}, B = {B}, S = {S}, n_embd = {c.n_embd}")
+    if fmt == "mxfp4" and decode_fused:
+        raise ValueError("generate: decode_fused=True with decode_weights='mxfp4': the LayerNorm-prologue kernels read "
+                         "bf16 or fp8 weights only")
     if kv_cache not in (None, "bf16", "fp8"):
         raise ValueError(f"generate: kv_cache must be 'bf16' or 'fp8', got {kv_cache!r}")
     have = getattr(cache, "dtype", None)                # None: the cache follows a passed cache=, else it is bf16
@@ -187,7 +207,8 @@ class Replay:
 
 class Engine:
     """One call's GPU model: the cache (``cache`` if it fits, reset; else a new one), bf16 shadows, block parameters.
-    ``dec`` (a :class:`DecodeWeights`): ``rows`` and every LM-head GEMM run on its fp8 pairs; prefill and extend blocks
+    ``dec`` (a :class:`DecodeWeights`): ``rows`` and every LM-head GEMM run on its stored weights, the kernel chosen by
+    their type (BL.linear_fwd_decode: K.gemm_skinny_fp8 or K.gemm_skinny_fp4); prefill and extend blocks
     keep the bf16 shadows.  ``kv``: the storage of a new cache (check_args has held a passed one against it); the blocks
     take their attention kernels from the cache.  ``fused`` (``decode_fused``): ``rows`` runs TX.block_step(fused=True);
     ln_f and the LM head stay two launches (fused, the 3144-block head lost: profiles/decode_fused.txt)."""
@@ -279,8 +300,8 @@ class Reference:
         self.rt = (lambda t: t) if kv == "bf16" else \
             (lambda t: dequantize_rows(*quantize_rows_reference(t.reshape(-1, t.shape[-1])), dtype=t.dtype).view_as(t))
         dt = self.tr.wte.weight.dtype
-        self.dq = None if dec is None else [[dequantize_rows(*pr, dtype=dt) for pr in blk] for blk in dec.blocks]
-        self.head = model.lm_head.weight if dec is None else dequantize_rows(*dec.wte, dtype=dt)
+        self.dq = None if dec is None else [[dec.dequantize(pr, dt) for pr in blk] for blk in dec.blocks]
+        self.head = model.lm_head.weight if dec is None else dec.dequantize(dec.wte, dt)
         w, self.H, self.hd = self.tr.wte.weight, self.c.n_head, self.c.n_embd // self.c.n_head
         self.ks = [torch.zeros(B, self.H, Tmax, self.hd, device=w.device, dtype=w.dtype) for _ in self.tr.h]
         self.vs = [torch.zeros_like(k) for k in self.ks]
@@ -491,9 +512,9 @@ class Session:
     same call re-runs ``generate`` on the concatenated history, which is the definition the GPU path is held to."""
 
     def __init__(self, model, B, max_len, S=1, decode_weights="bf16", kv_cache="bf16", decode_fused=False):
-        if decode_weights not in ("bf16", "fp8") or kv_cache not in ("bf16", "fp8"):
-            raise ValueError(f"session: decode_weights and kv_cache must be 'bf16' or 'fp8', got {decode_weights!r}, "
-                             f"{kv_cache!r}")
+        if decode_weights not in DECODE_WEIGHTS or kv_cache not in ("bf16", "fp8"):
+            raise ValueError(f"session: decode_weights must be 'bf16', 'fp8' or 'mxfp4' and kv_cache 'bf16' or 'fp8', got "
+                             f"{decode_weights!r}, {kv_cache!r}")
         if B < 1 or not 1 <= max_len <= model.config.block_size:
             raise ValueError(f"session: B >= 1 and 1 <= max_len <= block size {model.config.block_size}, got B = {B}, "
                              f"max_len = {max_len}")
@@ -502,7 +523,7 @@ class Session:
         self.history, self.cached = [[] for _ in range(B)], [0] * B
         self.cache = TX.KVCache(model, B, max_len, self.device, S=S, dtype=kv_cache) if self.device.type == "cuda" else None
         # quantised once, here: every turn runs on this snapshot of the weights
-        self.sampling = {"decode_weights": DecodeWeights(model)} if decode_weights == "fp8" else {}
+        self.sampling = {"decode_weights": DecodeWeights(model, decode_weights)} if decode_weights != "bf16" else {}
         self.sampling["kv_cache"] = kv_cache
         self.sampling["decode_fused"] = bool(decode_fused)
 

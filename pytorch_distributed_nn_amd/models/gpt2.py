@@ -337,6 +337,13 @@ class GPT2(nn.Module):
         Every ``"fp8"`` call quantises again; a ``generation.DecodeWeights(model)`` made once may be passed instead (a
         snapshot of the weights at that moment; :meth:`session` keeps one).
 
+        ``decode_weights="mxfp4"``: the same five weights as OCP microscaling fp4, e2m1 codes with one power-of-two
+        (e8m0) scale per 32 consecutive reduction elements, 4.25 bits per weight (``ops/quant.py``; ``csrc/kernels/
+        gemm_skinny_fp4.hip`` quantises and streams them, ``ops.kernels.gemm_skinny_fp4``).  Everything said of ``"fp8"``
+        holds: the dequantised weights are exactly bf16 numbers, the CPU path is the reference, speculation, graph replay,
+        resume and ``kv_cache`` are unchanged, and a ``generation.DecodeWeights(model, "mxfp4")`` may be passed.  It needs
+        n_embd % 32 == 0 as well, and ``decode_fused=True`` is refused with it (no prologue kernel reads this format).
+
         ``kv_cache="fp8"``: the key/value cache holds OCP e4m3fn codes with one power-of-two scale per 64-element row of K
         and of V (one layer, sequence, head and slot; the rule of ``ops/quant.py``), 68 bytes per row instead of 128
         (``ops.transformer.KVCache(dtype="fp8")``; the kernels of ``csrc/kernels/attention_cache_fp8.hip``).  Every key
@@ -397,7 +404,7 @@ class GPT2(nn.Module):
     def session(self, B, max_len, S=1, decode_weights="bf16", kv_cache="bf16", decode_fused=False):
         """A :class:`generation.Session`: B conversations of up to ``max_len`` tokens whose key/value cache is kept from
         one ``session.generate(turns, max_new_tokens, ...)`` to the next (``S``: the largest ``speculate`` to be used).
-        ``decode_weights="fp8"`` (see :meth:`generate`) quantises once, here; every turn reuses that set, which is a
+        ``decode_weights="fp8"`` or ``"mxfp4"`` (see :meth:`generate`) quantises once, here; every turn reuses that set, which is a
         snapshot of the weights at this moment: a later update of the model does not reach it.  ``kv_cache="fp8"``: the
         kept cache stores e4m3 codes (see :meth:`generate`).  ``decode_fused``: every turn's steps run the fused
         sequence (see :meth:`generate`)."""

@@ -139,6 +139,10 @@ _SIGS = {
     "pdnn_quant_rows_e4m3": [P, I, I, P, P, P],
     "pdnn_gemm_skinny_fp8": [P, L, P, P, P, L, I, I, I, P, I, P, P],
     "pdnn_gemm_skinny_fp8_plan": [I, I],
+    "pdnn_quant_blocks_mxfp4": [P, I, I, P, P, P],
+    "pdnn_gemm_skinny_fp4": [P, L, P, P, P, L, I, I, I, P, I, P, P],
+    "pdnn_gemm_skinny_fp4_rg": [P, L, P, P, P, L, I, I, I, P, I, P, I, P],     # (a launcher: not named *_groups, which _Lib memoises)
+    "pdnn_gemm_skinny_fp4_plan": [I, I],
     "pdnn_gemm_skinny_ln": [P, L, P, P, F, P, P, L, I, I, I, P, I, P, P],
     "pdnn_gemm_skinny_ln_fp8": [P, L, P, P, F, P, P, P, L, I, I, I, P, I, P, P],
     "pdnn_layernorm_fwd": [P, P, P, P, P, P, I, I, F, P],

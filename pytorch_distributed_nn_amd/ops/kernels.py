@@ -12,6 +12,7 @@ import ctypes
 import torch
 
 from ._backend import _CUR_DEV, HipError, call, lib, ptr, stream
+from .quant import Mxfp4Blocks
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -1432,6 +1433,54 @@ def gemm_skinny_fp8(x, q, inv, bias=None, act=0, res=None, out=None):
     return out
 
 
+def quant_blocks_mxfp4(w):
+    """w bf16 [N][K] contiguous -> (q uint8 [N][K / 2] e2m1 codes, two per byte, sc uint8 [N][K / 32] e8m0 block scales):
+    the MXFP4 format of ops/quant.py, computed by csrc/kernels/gemm_skinny_fp4.hip.  K % 32 == 0, N % 8 == 0."""
+    _chk(torch.is_tensor(w) and w.dtype == BF16 and w.is_cuda and w.dim() == 2 and w.is_contiguous()
+         and w.data_ptr() % 16 == 0, "quant_blocks_mxfp4: w must be a contiguous 16-byte aligned 2-D CUDA bf16 tensor")
+    N, K = w.shape
+    _chk(K >= 32 and K % 32 == 0 and N >= 8 and N % 8 == 0, f"quant_blocks_mxfp4: K % 32 == 0, N % 8 == 0, got {tuple(w.shape)}")
+    q = torch.empty(N, K // 2, device=w.device, dtype=torch.uint8)
+    sc = torch.empty(N, K // 32, device=w.device, dtype=torch.uint8)
+    call("pdnn_quant_blocks_mxfp4", ptr(w), N, K, ptr(q), ptr(sc), stream())
+    return q, sc
+
+
+def gemm_skinny_fp4(x, q, sc, bias=None, act=0, res=None, out=None, groups=0):
+    """:func:`gemm_skinny` on a weight stored as MXFP4: y = act(x @ dq^T + bias) (+res), dq[n][k] = value(q[n][k])
+    2^(sc[n][k / 32] - 127) (csrc/kernels/gemm_skinny_fp4.hip).  x bf16 [M][K] (row-strided), 1 <= M <= 64, q uint8
+    [N][K / 2] and sc uint8 [N][K / 32] contiguous, K % 32 == 0, N % 8 == 0; bias, act, res, out as there.  ``groups``: 16-row
+    weight groups per wave, 0 = the kernel's rule, 1 or (M <= 32) 2 for the measuring tools; the bits do not depend on it.
+    Row b does not depend on M or on the other rows."""
+    _chk(torch.is_tensor(x) and x.dtype == BF16 and x.is_cuda and x.dim() == 2 and x.data_ptr() % 16 == 0,
+         "gemm_skinny_fp4: x must be a 16-byte aligned 2-D CUDA bf16 tensor")
+    M, K = x.shape
+    _chk(1 <= M <= SKINNY_ROWS, f"gemm_skinny_fp4: 1 <= M <= {SKINNY_ROWS}, got M = {M}")
+    _chk(K >= 32 and K % 32 == 0, f"gemm_skinny_fp4: K % 32 == 0, got x {tuple(x.shape)}")
+    _chk(torch.is_tensor(q) and q.dtype == torch.uint8 and q.dim() == 2 and q.device == x.device and q.is_contiguous()
+         and q.data_ptr() % 16 == 0 and q.shape[1] == K // 2 and q.shape[0] >= 8 and q.shape[0] % 8 == 0,
+         f"gemm_skinny_fp4: q must be contiguous 16-byte aligned uint8 [N][{K // 2}] on x's device, N % 8 == 0")
+    N = q.shape[0]
+    _chk(torch.is_tensor(sc) and sc.dtype == torch.uint8 and sc.shape == (N, K // 32) and sc.is_contiguous()
+         and sc.device == x.device, f"gemm_skinny_fp4: sc must be contiguous uint8 [{N}][{K // 32}]")
+    _chk(x.stride(1) == 1 and x.stride(0) >= K and x.stride(0) % 8 == 0, "gemm_skinny_fp4: x rows contiguous, row stride % 8 == 0")
+    _chk(act in (0, 2), f"gemm_skinny_fp4: act must be 0 or 2 (GELU), got {act!r}")
+    _chk(groups in (0, 1) or (groups == 2 and M <= 32), f"gemm_skinny_fp4: groups must be 0, 1 or (M <= 32) 2, got {groups!r}")
+    _chk(bias is None or (bias.dtype == F32 and bias.shape == (N,) and bias.is_contiguous()
+                          and bias.device == x.device), f"gemm_skinny_fp4: bias must be contiguous fp32 [{N}]")
+    if out is None:
+        out = torch.empty(M, N, device=x.device, dtype=BF16)
+    _chk(out.dtype == BF16 and out.shape == (M, N) and out.device == x.device and out.stride(1) == 1
+         and out.stride(0) >= N and out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0,
+         f"gemm_skinny_fp4: out must be bf16 [{M}][{N}], rows contiguous, row stride % 8 == 0")
+    _chk(res is None or (res.dtype == BF16 and res.device == x.device and res.shape == out.shape
+                         and res.stride() == out.stride() and res.data_ptr() % 16 == 0),
+         "gemm_skinny_fp4: res must be bf16 of out's shape and strides")
+    call("pdnn_gemm_skinny_fp4_rg", ptr(x), x.stride(0), ptr(q), ptr(sc), ptr(out), out.stride(0), M, N, K, ptr(bias),
+         int(act), ptr(res), int(groups), stream())
+    return out
+
+
 FUSED_ROWS = 16             # rows the prologue kernel of csrc/kernels/gemm_skinny_pro.hip takes: one MFMA tile
 FUSED_MAX_D = 2048          # and its reduction length, the model width: layernorm_fwd's own limit
 
@@ -1447,6 +1496,7 @@ def gemm_skinny_ln(x, gamma, beta, eps, w, bias=None, act=0, out=None, image=Non
          "gemm_skinny_ln: x must be a 16-byte aligned 2-D CUDA bf16 tensor")
     M, D = x.shape
     dev = x.device
+    _chk(not isinstance(w, Mxfp4Blocks), "gemm_skinny_ln: MXFP4 weights (ops.quant.Mxfp4Blocks) have no prologue kernel")
     fp8 = isinstance(w, tuple)
     wt, dt, dq = (w[0], torch.uint8, 16) if fp8 else (w, BF16, 8)
     _chk(1 <= M <= FUSED_ROWS, f"gemm_skinny_ln: 1 <= M <= {FUSED_ROWS}, got M = {M}")

@@ -23,6 +23,7 @@ import torch
 from .. import tuning as _tuning
 from . import kernels as K
 from .functional import weight_bf16_t
+from .quant import Mxfp4Blocks
 
 F32 = torch.float32
 
@@ -38,7 +39,12 @@ def linear_fwd_decode(x, wk, bias=None, act=0, res=None):
     weight-streaming kernel (``kernels.gemm_skinny``, csrc/kernels/gemm_skinny.hip) unless tuning ``decode_skinny``
     is 0; everything else is :func:`linear_fwd`.  ``wk`` may also be a pair (q, inv), the weight stored as e4m3fn
     codes with row scales (ops/quant.py): it runs ``kernels.gemm_skinny_fp8`` for every M up to ``kernels.SKINNY_ROWS``
-    and has no other engine, so more rows are refused."""
+    and has no other engine, so more rows are refused.  An ``ops.quant.Mxfp4Blocks`` (q, sc), the weight as e2m1 codes
+    with block scales, runs ``kernels.gemm_skinny_fp4`` under the same rule."""
+    if isinstance(wk, Mxfp4Blocks):
+        if x.shape[0] > K.SKINNY_ROWS:
+            raise ValueError(f"linear_fwd_decode: mxfp4 decode weights take at most {K.SKINNY_ROWS} rows, got {x.shape[0]}")
+        return K.gemm_skinny_fp4(x, wk.q, wk.sc, bias=bias, act=act, res=res)
     if isinstance(wk, tuple):
         if x.shape[0] > K.SKINNY_ROWS:
             raise ValueError(f"linear_fwd_decode: fp8 decode weights take at most {K.SKINNY_ROWS} rows, got {x.shape[0]}")

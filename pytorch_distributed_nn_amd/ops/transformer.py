@@ -583,7 +583,8 @@ def block_step(x, conf, shadows, params, cache, layer, S=1, fused=False):
     BL.linear_fwd_decode and K.attn_decode.  S > 1, a speculative verify step: K.attn_decode_multi, and K.gemm_skinny
     for every M = B*S <= K.SKINNY_ROWS, whose row bits do not depend on M: a row gets the bits of the S == 1 step.
     ``shadows`` of pairs (q, inv) (ops/quant.py) run the four linears on K.gemm_skinny_fp8 for S == 1 and S > 1 alike: the
-    same kernel, row bits independent of M.  An fp8 ``cache`` runs K.attn_decode_fp8 / K.attn_decode_multi_fp8.
+    same kernel, row bits independent of M; ``shadows`` of ops.quant.Mxfp4Blocks run them on K.gemm_skinny_fp4 likewise.
+    An fp8 ``cache`` runs K.attn_decode_fp8 / K.attn_decode_multi_fp8.
     ``fused=True`` (at most K.FUSED_ROWS rows): :func:`_block_step_fused`, six launches instead of eight, for every S,
     weight format and cache dtype; its row bits do not depend on the row count either."""
     B, _, H, eps = conf[:4]
@@ -597,7 +598,7 @@ def block_step(x, conf, shadows, params, cache, layer, S=1, fused=False):
             raise ValueError(f"block_verify: {x.shape[0]} rows for B = {B}, S = {S} (cache S = {cache.S}, at most "
                              f"{K.SKINNY_ROWS} rows)")
         lin, attn, multi = K.gemm_skinny, K.attn_decode_multi_fp8 if fp8 else K.attn_decode_multi, {"S": S}
-    if isinstance(shadows[0], tuple):       # fp8 decode weights, pairs (q, inv): one kernel for every row count
+    if isinstance(shadows[0], tuple):       # quantised decode weights (ops/quant.py): one kernel for every row count
         lin = BL.linear_fwd_decode
     step = _block_step_fused if fused else _block_infer
     return step(x, eps, shadows, params, lin, attn, *cache.layer(layer), cache.lens, chunk=cache.chunk,

@@ -60,9 +60,9 @@ def build_parser():
     ap.add_argument("--chunk", type=int, default=None, metavar="C",
                     help="ingest the prompt in pieces of C tokens through generate(resume=True) on a kept cache before "
                          "sampling (GPU; the CPU path keeps no cache and runs the prompt in one piece)")
-    ap.add_argument("--decode-weights", choices=["bf16", "fp8"], default="bf16",
-                    help="fp8: the decode steps stream the block linears and the LM head as e4m3 codes with row scales "
-                         "(weight-only; GPT2.generate)")
+    ap.add_argument("--decode-weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
+                    help="fp8: the decode steps stream the block linears and the LM head as e4m3 codes with row scales; "
+                         "mxfp4: as e2m1 codes with one scale per 32 elements (weight-only; GPT2.generate)")
     ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: the key/value cache holds e4m3 codes with one scale per 64-element row (GPT2.generate)")
     ap.add_argument("--decode-fused", action="store_true",
