@@ -40,9 +40,9 @@ def sample(logits, temperature, top_k, generator, top_p=None):
 
 # one checked call: N = max_new_tokens, pl = the B prompt lengths, draw = dict(temperature, top_k, top_p), seed masked to
 # 63 bits (sampler="device", else None), S = speculate or None, guess = the draft table or None (n-gram drafts), kv = the
-# cache's storage, "bf16" or "fp8", fused = decode_fused
+# cache's storage, "bf16" or "fp8", fused = decode_fused, prefill_dec = prefill_weights == "decode"
 Request = namedtuple("Request", "B P N pl draw eos generator seed S guess ngram graph return_logits return_stats cache "
-                     "resume decode_weights kv fused", defaults=(False, "bf16", "bf16", False))
+                     "resume decode_weights kv fused prefill_dec", defaults=(False, "bf16", "bf16", False, False))
 
 
 DECODE_WEIGHTS = ("bf16", "fp8", "mxfp4")
@@ -84,7 +84,7 @@ class DecodeWeights:
 
 def check_args(c, idx, max_new_tokens, *, temperature, top_k, eos_token, prompt_lens, generator, graph,
                return_logits, cache, top_p, sampler, seed, speculate, draft, ngram, return_stats, resume=False,
-               decode_weights="bf16", kv_cache=None, decode_fused=False):
+               decode_weights="bf16", kv_cache=None, decode_fused=False, prefill_weights="bf16"):
     """``generate``'s arguments and the model's config ``c`` -> :class:`Request`, or the first refusal in this order"""
     if idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
         raise ValueError(f"generate: idx must be [B][P] with B, P >= 1, got {tuple(idx.shape)}")
@@ -151,6 +151,11 @@ def check_args(c, idx, max_new_tokens, *, temperature, top_k, eos_token, prompt_
     if fmt == "mxfp4" and decode_fused:
         raise ValueError("generate: decode_fused=True with decode_weights='mxfp4': the LayerNorm-prologue kernels read "
                          "bf16 or fp8 weights only")
+    if prefill_weights not in ("bf16", "decode"):
+        raise ValueError(f"generate: prefill_weights must be 'bf16' or 'decode', got {prefill_weights!r}")
+    if prefill_weights == "decode" and fmt == "bf16":
+        raise ValueError("generate: prefill_weights='decode' runs the prefill on the stored decode weights: it needs "
+                         "decode_weights 'fp8', 'mxfp4' or a DecodeWeights")
     if kv_cache not in (None, "bf16", "fp8"):
         raise ValueError(f"generate: kv_cache must be 'bf16' or 'fp8', got {kv_cache!r}")
     have = getattr(cache, "dtype", None)                # None: the cache follows a passed cache=, else it is bf16
@@ -165,7 +170,7 @@ def check_args(c, idx, max_new_tokens, *, temperature, top_k, eos_token, prompt_
     return Request(B, P, max_new_tokens, pl, dict(temperature=float(temperature), top_k=top_k, top_p=top_p), eos_token,
                    generator, int(seed) & ((1 << 63) - 1) if sampler == "device" else None, S, guess, ngram, graph,
                    return_logits, return_stats, cache, bool(resume), decode_weights, kv_cache or have or "bf16",
-                   bool(decode_fused))
+                   bool(decode_fused), prefill_weights == "decode")
 
 
 def check_resume(c, idx, B, pl, N, S, cache):
@@ -209,11 +214,12 @@ class Engine:
     """One call's GPU model: the cache (``cache`` if it fits, reset; else a new one), bf16 shadows, block parameters.
     ``dec`` (a :class:`DecodeWeights`): ``rows`` and every LM-head GEMM run on its stored weights, the kernel chosen by
     their type (BL.linear_fwd_decode: K.gemm_skinny_fp8 or K.gemm_skinny_fp4); prefill and extend blocks
-    keep the bf16 shadows.  ``kv``: the storage of a new cache (check_args has held a passed one against it); the blocks
+    keep the bf16 shadows unless ``prefill_dec`` (``prefill_weights="decode"``), which runs them on the stored weights
+    too (BL.linear_fwd_wq: K.gemm_wq_fp8 or K.gemm_wq_fp4), one model for the whole call.  ``kv``: the storage of a new cache (check_args has held a passed one against it); the blocks
     take their attention kernels from the cache.  ``fused`` (``decode_fused``): ``rows`` runs TX.block_step(fused=True);
     ln_f and the LM head stay two launches (fused, the 3144-block head lost: profiles/decode_fused.txt)."""
 
-    def __init__(self, model, B, P, N, S=1, cache=None, resume=False, dec=None, kv="bf16", fused=False):
+    def __init__(self, model, B, P, N, S=1, cache=None, resume=False, dec=None, kv="bf16", fused=False, prefill_dec=False):
         self.config, tr = model.config, model.transformer
         dev = tr.wte.weight.device
         Tneed = model.kv_cache_len(P, N + (S if S > 1 else 0))       # rejected drafts occupy slots past the accepted length
@@ -235,6 +241,7 @@ class Engine:
         self.step_blocks, self.head = self.blocks, self.wte_k        # what ``rows`` and the LM head read
         if dec is not None:
             self.step_blocks, self.head = [(p, pairs) for (p, _), pairs in zip(self.blocks, dec.blocks)], dec.wte
+        self.ingest_blocks = self.step_blocks if prefill_dec else self.blocks       # what ``prefill`` and ``extend`` read
 
     def prefill(self, idx, pl_dev):
         """idx int64 [B][P], pl_dev int32 [B] -> bf16 logits [B][V] at each prompt's last position; cache.lens = pl_dev"""
@@ -245,7 +252,7 @@ class Engine:
         if Tp > c.block_size:
             wpe_p = torch.cat([wpe_p, wpe_p[-1:].expand(Tp - c.block_size, -1)]).contiguous()
         x = K.embedding_fwd(F.pad(idx, (0, Tp - P)).reshape(-1).contiguous(), self.wte_k, wpe_p, Tp)
-        for layer, (params, shadows) in enumerate(self.blocks):
+        for layer, (params, shadows) in enumerate(self.ingest_blocks):
             x = TX.block_prefill(x, (B, Tp, c.n_head, c.eps), shadows, params, cache, layer)
         last = torch.arange(B, device=idx.device) * Tp + pl_dev.long() - 1
         xf, _, _ = K.layernorm_fwd(x.index_select(0, last), self.lnw, self.lnb, c.eps)
@@ -262,7 +269,7 @@ class Engine:
         Tq = -(-P // K.EXTEND_TILE) * K.EXTEND_TILE
         pos = (cache.lens[:, None] + torch.arange(Tq, device=idx.device, dtype=torch.int32)[None, :]).reshape(-1)
         x = K.embedding_decode(F.pad(idx, (0, Tq - P)).reshape(-1).contiguous(), pos.contiguous(), self.wte_k, self.wpe_k)
-        for layer, (params, shadows) in enumerate(self.blocks):
+        for layer, (params, shadows) in enumerate(self.ingest_blocks):
             x = TX.block_extend(x, (B, Tq, c.n_head, c.eps), shadows, params, cache, layer)
         last = torch.arange(B, device=idx.device) * Tq + pl_dev.long() - 1
         xf, _, _ = K.layernorm_fwd(x.index_select(0, last), self.lnw, self.lnb, c.eps)
@@ -290,13 +297,15 @@ class Engine:
 class Reference:
     """One call's CPU model (plain PyTorch, any head dim), the numerics reference of :class:`Engine`; ``lens`` int64 [B].
     ``dec`` (a :class:`DecodeWeights`): ``step`` and the logits after the prefill run with the dequantised weights dq in
-    place of the four block linears and the LM head; the prefill's blocks and the embeddings keep the originals.
+    place of the four block linears and the LM head; the prefill's blocks and the embeddings keep the originals, unless
+    ``prefill_dec`` (``prefill_weights="decode"``): then the prefill's four linears of every block are dq as well.
     ``kv="fp8"``: every K and V row (one layer, sequence, head, slot) is stored as dequantize_rows(*
     quantize_rows_reference(row)), and a step attends to its new token's stored row; the prefill's own attention reads the
     prompt's K and V as they are."""
 
-    def __init__(self, model, B, Tmax, dec=None, kv="bf16"):
+    def __init__(self, model, B, Tmax, dec=None, kv="bf16", prefill_dec=False):
         self.model, self.c, self.tr = model, model.config, model.transformer
+        self.prefill_dec = prefill_dec
         self.rt = (lambda t: t) if kv == "bf16" else \
             (lambda t: dequantize_rows(*quantize_rows_reference(t.reshape(-1, t.shape[-1])), dtype=t.dtype).view_as(t))
         dt = self.tr.wte.weight.dtype
@@ -313,12 +322,15 @@ class Reference:
         B, P = idx.shape
         self.lens = pl_dev.long().clone()
         x = tr.wte(idx) + tr.wpe(torch.arange(P, device=idx.device).clamp(max=c.block_size - 1))
-        for blk, kc, vc in zip(tr.h, self.ks, self.vs):
-            q, k, v = (t.view(B, P, H, hd).transpose(1, 2) for t in blk.attn.c_attn(blk.ln_1(x)).split(c.n_embd, dim=2))
+        for i, (blk, kc, vc) in enumerate(zip(tr.h, self.ks, self.vs)):
+            mods = (blk.attn.c_attn, blk.attn.c_proj, blk.mlp.c_fc, blk.mlp.c_proj)
+            wq, wp, wf, wf2 = self.dq[i] if self.prefill_dec else (m.weight for m in mods)
+            q, k, v = (t.view(B, P, H, hd).transpose(1, 2)
+                       for t in F.linear(blk.ln_1(x), wq, mods[0].bias).split(c.n_embd, dim=2))
             kc[:, :, :P], vc[:, :, :P] = self.rt(k), self.rt(v)
             y = F.scaled_dot_product_attention(q, k, v, is_causal=True)
-            x = x + blk.attn.c_proj(y.transpose(1, 2).reshape(B, P, c.n_embd))
-            x = x + blk.mlp(blk.ln_2(x))
+            x = x + F.linear(y.transpose(1, 2).reshape(B, P, c.n_embd), wp, mods[1].bias)
+            x = x + F.linear(F.gelu(F.linear(blk.ln_2(x), wf, mods[2].bias), approximate="tanh"), wf2, mods[3].bias)
         return F.linear(tr.ln_f(x[self.ar, self.lens - 1]), self.head).float()
 
     def step(self, tok):
@@ -340,11 +352,11 @@ class Reference:
 
 
 def fused_stepper(model, idx, pl_dev, max_new_tokens, graph=False, cache=None, resume=False, dec=None, kv="bf16",
-                  fused=False):
+                  fused=False, prefill_dec=False):
     """GPU: prefill -> (fp32 logits [B][V] at each prompt's last position, step(tok) -> the next logits, in one fp32
     buffer).  The engine of the torch-sampler loop: the token comes from the host side of the loop."""
     B, P = idx.shape
-    eng = Engine(model, B, P, max_new_tokens, 1, cache, resume, dec, kv, fused)
+    eng = Engine(model, B, P, max_new_tokens, 1, cache, resume, dec, kv, fused, prefill_dec)
     logits16 = eng.ingest(idx, pl_dev, resume)
     tok_buf = torch.zeros(B, dtype=torch.int64, device=idx.device)
     logits = logits16.float()
@@ -426,7 +438,7 @@ def _speculate_reference(model, r, idx, pl_dev, out, dec=None):
     (a position the row never reaches is clamped to the last slot, which no emitted token reads); then lens = accepted"""
     B, P, N, S = r.B, r.P, r.N, r.S
     Tmax = max(r.pl) + N
-    ref = Reference(model, B, Tmax, dec, r.kv)
+    ref = Reference(model, B, Tmax, dec, r.kv, r.prefill_dec)
     finished = torch.zeros(B, dtype=torch.uint8, device=idx.device) if r.eos is not None else None
     out[:, P], _, _ = sample_reference(ref.prefill(idx, pl_dev), state=(r.seed, 0), finished=finished, eos_token=r.eos,
                                        **r.draw)
@@ -454,9 +466,10 @@ def generate(model, idx, max_new_tokens, **kw):
     B, P, N = r.B, r.P, r.N
     idx = idx.long()
     out = torch.cat([idx, idx.new_zeros(B, N)], 1)
-    dec = DecodeWeights.of(model, r.decode_weights) if N else None      # an ingest-only call draws from no logits
+    # an ingest-only call draws from no logits: it needs the stored weights only where its blocks read them
+    dec = DecodeWeights.of(model, r.decode_weights) if N or r.prefill_dec else None
     if N == 0 and r.resume:                             # chunked prefill: the ingest is the whole call
-        Engine(model, B, P, 0, r.S or 1, r.cache, True, dec, r.kv).extend(idx, torch.tensor(r.pl, device=idx.device,
+        Engine(model, B, P, 0, r.S or 1, r.cache, True, dec, r.kv, False, r.prefill_dec).extend(idx, torch.tensor(r.pl, device=idx.device,
                                                                                  dtype=torch.int32))
     if N == 0:
         if r.return_stats:
@@ -466,7 +479,7 @@ def generate(model, idx, max_new_tokens, **kw):
     if r.guess is not None:
         r = r._replace(guess=r.guess.to(idx.device).contiguous())
     if r.seed is not None and idx.is_cuda:         # the sampling kernel is inside the step: the loop is on the device
-        eng = Engine(model, B, P, N, r.S or 1, r.cache, r.resume, dec, r.kv, r.fused)
+        eng = Engine(model, B, P, N, r.S or 1, r.cache, r.resume, dec, r.kv, r.fused, r.prefill_dec)
         logit_buf = eng.ingest(idx, pl_dev, r.resume)
         res = _speculate_device(eng, r, pl_dev, out, logit_buf) if r.S else _device_loop(eng, r, out, logit_buf)
         return (out, res) if r.return_logits or r.return_stats else out
@@ -475,9 +488,9 @@ def generate(model, idx, max_new_tokens, **kw):
         return (out, stats) if r.return_stats else out
     # the token is drawn on the host side of the loop: the torch sampler on both devices, the device sampler's reference
     if idx.is_cuda:
-        logits, step = fused_stepper(model, idx, pl_dev, N, r.graph, r.cache, r.resume, dec, r.kv, r.fused)
+        logits, step = fused_stepper(model, idx, pl_dev, N, r.graph, r.cache, r.resume, dec, r.kv, r.fused, r.prefill_dec)
     else:
-        ref = Reference(model, B, max(r.pl) + N, dec, r.kv)
+        ref = Reference(model, B, max(r.pl) + N, dec, r.kv, r.prefill_dec)
         logits, step = ref.prefill(idx, pl_dev), ref.step
     finished = torch.zeros(B, dtype=torch.bool, device=idx.device)      # rows that have emitted eos_token
     if r.seed is not None:                                              # sample_reference: uint8 flags, None without eos
@@ -511,7 +524,11 @@ class Session:
     it: a turn costs its own tokens against the cache, not the whole history again.  On the CPU there is no cache: the
     same call re-runs ``generate`` on the concatenated history, which is the definition the GPU path is held to."""
 
-    def __init__(self, model, B, max_len, S=1, decode_weights="bf16", kv_cache="bf16", decode_fused=False):
+    def __init__(self, model, B, max_len, S=1, decode_weights="bf16", kv_cache="bf16", decode_fused=False,
+                 prefill_weights="bf16"):
+        if prefill_weights not in ("bf16", "decode") or (prefill_weights == "decode" and decode_weights == "bf16"):
+            raise ValueError(f"session: prefill_weights must be 'bf16' or, with quantised decode_weights, 'decode'; got "
+                             f"{prefill_weights!r} with decode_weights={decode_weights!r}")
         if decode_weights not in DECODE_WEIGHTS or kv_cache not in ("bf16", "fp8"):
             raise ValueError(f"session: decode_weights must be 'bf16', 'fp8' or 'mxfp4' and kv_cache 'bf16' or 'fp8', got "
                              f"{decode_weights!r}, {kv_cache!r}")
@@ -526,6 +543,7 @@ class Session:
         self.sampling = {"decode_weights": DecodeWeights(model, decode_weights)} if decode_weights != "bf16" else {}
         self.sampling["kv_cache"] = kv_cache
         self.sampling["decode_fused"] = bool(decode_fused)
+        self.sampling["prefill_weights"] = prefill_weights
 
     def generate(self, turns, max_new_tokens, *, eos_token=None, **sampling):
         """``turns``: B token sequences (lists or 1-D tensors), row b's next turn; it may be empty only where the row has

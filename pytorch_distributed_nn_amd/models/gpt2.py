@@ -304,7 +304,7 @@ class GPT2(nn.Module):
     def generate(self, idx, max_new_tokens, *, temperature=1.0, top_k=None, eos_token=None, prompt_lens=None,
                  generator=None, graph=False, return_logits=False, cache=None, top_p=None, sampler="torch", seed=None,
                  speculate=None, draft="ngram", ngram=3, return_stats=False, resume=False, decode_weights="bf16",
-                 kv_cache=None, decode_fused=False):
+                 kv_cache=None, decode_fused=False, prefill_weights="bf16"):
         """Sample ``max_new_tokens`` tokens after the prompts ``idx`` int [B][P] with a key/value cache: one prefill over
         the prompt, then one single-token step per new token (GPU: ``ops.transformer.block_step`` on the decode
         attention kernel of ``csrc/kernels/attention_decode.hip``; CPU: plain PyTorch in fp32 with per-layer k, v lists,
@@ -343,6 +343,17 @@ class GPT2(nn.Module):
         holds: the dequantised weights are exactly bf16 numbers, the CPU path is the reference, speculation, graph replay,
         resume and ``kv_cache`` are unchanged, and a ``generation.DecodeWeights(model, "mxfp4")`` may be passed.  It needs
         n_embd % 32 == 0 as well, and ``decode_fused=True`` is refused with it (no prologue kernel reads this format).
+
+        ``prefill_weights="decode"`` (needs quantised ``decode_weights``): the prefill and extend blocks run on the
+        stored weights too, so the whole call is one model, the bf16 model with the dequantised weights dq in the four
+        linears of every block and the LM head: a prompt token's K / V rows are those a decode step would have stored
+        for it, whether it was ingested by the prefill, by ``resume=True`` in any chunking, or generated.  GPU:
+        ``ops.linear.linear_fwd_wq`` on the wide-M weight-only GEMM of ``csrc/kernels/gemm_wq.hip`` (``ops.kernels.
+        gemm_wq_fp8`` / ``gemm_wq_fp4``), which reads the codes, converts them once per block on their way into LDS and
+        keeps one accumulator per output element over K in order: a row's bits depend neither on the row count nor on
+        the other rows.  The CPU path computes the same definition (its reference).  Embeddings, ``ln_f`` and the LM
+        head are as without it.  The default ``"bf16"`` is the behaviour described above, bit for bit; ``"decode"`` with
+        ``decode_weights="bf16"`` is refused.
 
         ``kv_cache="fp8"``: the key/value cache holds OCP e4m3fn codes with one power-of-two scale per 64-element row of K
         and of V (one layer, sequence, head and slot; the rule of ``ops/quant.py``), 68 bytes per row instead of 128
@@ -399,16 +410,17 @@ class GPT2(nn.Module):
                           prompt_lens=prompt_lens, generator=generator, graph=graph, return_logits=return_logits,
                           cache=cache, top_p=top_p, sampler=sampler, seed=seed, speculate=speculate, draft=draft,
                           ngram=ngram, return_stats=return_stats, resume=resume, decode_weights=decode_weights,
-                          kv_cache=kv_cache, decode_fused=decode_fused)
+                          kv_cache=kv_cache, decode_fused=decode_fused, prefill_weights=prefill_weights)
 
-    def session(self, B, max_len, S=1, decode_weights="bf16", kv_cache="bf16", decode_fused=False):
+    def session(self, B, max_len, S=1, decode_weights="bf16", kv_cache="bf16", decode_fused=False, prefill_weights="bf16"):
         """A :class:`generation.Session`: B conversations of up to ``max_len`` tokens whose key/value cache is kept from
         one ``session.generate(turns, max_new_tokens, ...)`` to the next (``S``: the largest ``speculate`` to be used).
         ``decode_weights="fp8"`` or ``"mxfp4"`` (see :meth:`generate`) quantises once, here; every turn reuses that set, which is a
         snapshot of the weights at this moment: a later update of the model does not reach it.  ``kv_cache="fp8"``: the
         kept cache stores e4m3 codes (see :meth:`generate`).  ``decode_fused``: every turn's steps run the fused
-        sequence (see :meth:`generate`)."""
-        return G.Session(self, B, max_len, S, decode_weights, kv_cache, decode_fused)
+        sequence (see :meth:`generate`).  ``prefill_weights="decode"``: every turn is ingested on the stored weights
+        (see :meth:`generate`)."""
+        return G.Session(self, B, max_len, S, decode_weights, kv_cache, decode_fused, prefill_weights)
 
     def _forward_reference(self, idx, targets=None, doc=None, drop=None):
         B, T = idx.shape

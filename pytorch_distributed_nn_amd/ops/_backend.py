@@ -143,6 +143,11 @@ _SIGS = {
     "pdnn_gemm_skinny_fp4": [P, L, P, P, P, L, I, I, I, P, I, P, P],
     "pdnn_gemm_skinny_fp4_rg": [P, L, P, P, P, L, I, I, I, P, I, P, I, P],     # (a launcher: not named *_groups, which _Lib memoises)
     "pdnn_gemm_skinny_fp4_plan": [I, I],
+    "pdnn_gemm_wq_fp8": [P, L, P, P, P, L, I, I, I, P, I, P, P],
+    "pdnn_gemm_wq_fp8_tile": [P, L, P, P, P, L, I, I, I, P, I, P, I, P],   # (launchers taking the tile, as *_rg above)
+    "pdnn_gemm_wq_fp4": [P, L, P, P, P, L, I, I, I, P, I, P, P],
+    "pdnn_gemm_wq_fp4_tile": [P, L, P, P, P, L, I, I, I, P, I, P, I, P],
+    "pdnn_gemm_wq_plan": [I, I],
     "pdnn_gemm_skinny_ln": [P, L, P, P, F, P, P, L, I, I, I, P, I, P, P],
     "pdnn_gemm_skinny_ln_fp8": [P, L, P, P, F, P, P, P, L, I, I, I, P, I, P, P],
     "pdnn_layernorm_fwd": [P, P, P, P, P, P, I, I, F, P],

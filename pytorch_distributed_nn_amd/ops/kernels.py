@@ -1481,6 +1481,55 @@ def gemm_skinny_fp4(x, q, sc, bias=None, act=0, res=None, out=None, groups=0):
     return out
 
 
+def _gemm_wq(name, entry, x, q, scl, scl_ok, gran, qcols, bias, act, res, out, tile):
+    """the checks and the launch :func:`gemm_wq_fp8` and :func:`gemm_wq_fp4` share: those of their skinny siblings
+    without the row limit.  ``scl_ok(N, K)``: the scale operand's own check; ``gran``: K's granularity; ``qcols(K)``:
+    bytes of a row of codes."""
+    _chk(torch.is_tensor(x) and x.dtype == BF16 and x.is_cuda and x.dim() == 2 and x.data_ptr() % 16 == 0,
+         f"{name}: x must be a 16-byte aligned 2-D CUDA bf16 tensor")
+    M, K = x.shape
+    _chk(M >= 1, f"{name}: M >= 1, got M = {M}")
+    _chk(K >= gran and K % gran == 0, f"{name}: K % {gran} == 0, got x {tuple(x.shape)}")
+    _chk(torch.is_tensor(q) and q.dtype == torch.uint8 and q.dim() == 2 and q.device == x.device and q.is_contiguous()
+         and q.data_ptr() % 16 == 0 and q.shape[1] == qcols(K) and q.shape[0] >= 8 and q.shape[0] % 8 == 0,
+         f"{name}: q must be contiguous 16-byte aligned uint8 [N][{qcols(K)}] on x's device, N % 8 == 0")
+    N = q.shape[0]
+    _chk(torch.is_tensor(scl) and scl.device == x.device and scl.is_contiguous() and scl_ok(N, K), f"{name}: scales of q")
+    _chk(x.stride(1) == 1 and x.stride(0) >= K and x.stride(0) % 8 == 0, f"{name}: x rows contiguous, row stride % 8 == 0")
+    _chk(act in (0, 2), f"{name}: act must be 0 or 2 (GELU), got {act!r}")
+    _chk(tile in (0, 64, 128), f"{name}: tile must be 0 (the kernel's rule), 64 or 128, got {tile!r}")
+    _chk(bias is None or (bias.dtype == F32 and bias.shape == (N,) and bias.is_contiguous()
+                          and bias.device == x.device), f"{name}: bias must be contiguous fp32 [{N}]")
+    if out is None:
+        out = torch.empty(M, N, device=x.device, dtype=BF16)
+    _chk(out.dtype == BF16 and out.shape == (M, N) and out.device == x.device and out.stride(1) == 1
+         and out.stride(0) >= N and out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0,
+         f"{name}: out must be bf16 [{M}][{N}], rows contiguous, row stride % 8 == 0")
+    _chk(res is None or (res.dtype == BF16 and res.device == x.device and res.shape == out.shape
+                         and res.stride() == out.stride() and res.data_ptr() % 16 == 0),
+         f"{name}: res must be bf16 of out's shape and strides")
+    call(entry, ptr(x), x.stride(0), ptr(q), ptr(scl), ptr(out), out.stride(0), M, N, K, ptr(bias), int(act), ptr(res),
+         int(tile), stream())
+    return out
+
+
+def gemm_wq_fp8(x, q, inv, bias=None, act=0, res=None, out=None, tile=0):
+    """y = act(x @ dq^T + bias) (+res) for any number of rows on a weight stored as e4m3fn codes, dq[n][k] = value(q[n][k])
+    inv[n] (csrc/kernels/gemm_wq.hip): :func:`gemm_skinny_fp8`'s operands and checks without its 64-row limit.  One fp32
+    accumulator per element over K in order, no split and no atomics: a row's bits depend neither on M, nor on the other
+    rows, nor on ``tile`` (0 = the kernel's rule of (M, N); 64 or 128 for the measuring tools)."""
+    return _gemm_wq("gemm_wq_fp8", "pdnn_gemm_wq_fp8_tile", x, q, inv, lambda N, K: inv.dtype == F32 and inv.shape == (N,),
+                    16, lambda K: K, bias, act, res, out, tile)
+
+
+def gemm_wq_fp4(x, q, sc, bias=None, act=0, res=None, out=None, tile=0):
+    """:func:`gemm_wq_fp8` on a weight stored as MXFP4 (q uint8 [N][K / 2], sc uint8 [N][K / 32], K % 32 == 0): the
+    operands and checks of :func:`gemm_skinny_fp4` without its 64-row limit."""
+    return _gemm_wq("gemm_wq_fp4", "pdnn_gemm_wq_fp4_tile", x, q, sc,
+                    lambda N, K: sc.dtype == torch.uint8 and sc.shape == (N, K // 32), 32, lambda K: K // 2, bias, act, res,
+                    out, tile)
+
+
 FUSED_ROWS = 16             # rows the prologue kernel of csrc/kernels/gemm_skinny_pro.hip takes: one MFMA tile
 FUSED_MAX_D = 2048          # and its reduction length, the model width: layernorm_fwd's own limit
 

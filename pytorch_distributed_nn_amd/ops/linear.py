@@ -54,6 +54,18 @@ def linear_fwd_decode(x, wk, bias=None, act=0, res=None):
     return linear_fwd(x, wk, bias=bias, act=act, res=res)
 
 
+def linear_fwd_wq(x, wk, bias=None, act=0, res=None):
+    """:func:`linear_fwd` (without ``aux``) for any number of rows on a weight in one of the stored forms of
+    ops/quant.py: an ``ops.quant.Mxfp4Blocks`` runs ``kernels.gemm_wq_fp4``, an ``Fp8Rows`` or a pair (q, inv)
+    ``kernels.gemm_wq_fp8`` (csrc/kernels/gemm_wq.hip): the prefill / extend sibling of :func:`linear_fwd_decode`, whose
+    kernels stop at ``kernels.SKINNY_ROWS`` rows.  A bf16 tensor falls through to :func:`linear_fwd`."""
+    if isinstance(wk, Mxfp4Blocks):
+        return K.gemm_wq_fp4(x, wk.q, wk.sc, bias=bias, act=act, res=res)
+    if isinstance(wk, tuple):
+        return K.gemm_wq_fp8(x, wk[0], wk[1], bias=bias, act=act, res=res)
+    return linear_fwd(x, wk, bias=bias, act=act, res=res)
+
+
 def linear_dgrad(g, wk, dgelu=None, p=None):
     """dX = g @ wk (wk stored [N][K] as in the forward); with ``dgelu`` = pre-activation u: dX *= gelu'(u).
 

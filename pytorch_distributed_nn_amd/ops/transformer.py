@@ -553,16 +553,18 @@ def _block_infer(x, eps, shadows, params, lin, attn, *args, **kw):
 def block_prefill(x, conf, shadows, params, cache, layer):
     """One block over the whole (padded) prompt: x bf16 [B*T][D], conf = (B, T, H, eps) or a :class:`BlockConf`,
     T % 128 == 0 -> x2; the K and V of every position also go into slots 0..T-1 of ``cache`` layer ``layer``.  The
-    linears are bf16 (BL.linear_fwd) whatever config.fp8 says."""
+    linears are bf16 (BL.linear_fwd) whatever config.fp8 says; ``shadows`` in a stored form of ops/quant.py (the test
+    :func:`block_step` makes) run them on the codes instead, BL.linear_fwd_wq (csrc/kernels/gemm_wq.hip)."""
     B, T, H, eps = conf[:4]
     need_fused_kernels(x.shape[1], H, T)
+    lin = BL.linear_fwd_wq if isinstance(shadows[0], tuple) else BL.linear_fwd
 
     fill = K.kv_cache_fill if cache.dtype == "bf16" else K.kv_cache_fill_fp8
 
     def attn(qkv):      # a prompt is one document, and nothing is dropped; it attends to its own unquantised K and V
         fill(qkv, *cache.layer(layer), B, T)
         return K.flash_attn_fwd(qkv, B, T, H, 1.0 / math.sqrt(x.shape[1] // H))[0]
-    return _block_infer(x, eps, shadows, params, BL.linear_fwd, attn)
+    return _block_infer(x, eps, shadows, params, lin, attn)
 
 
 def _block_step_fused(x, eps, shadows, params, lin, attn, *args, **kw):
@@ -608,8 +610,9 @@ def block_step(x, conf, shadows, params, cache, layer, S=1, fused=False):
 def block_extend(x, conf, shadows, params, cache, layer):
     """One block on Tq new tokens per sequence behind a non-empty cache: x bf16 [B*Tq][D], conf = (B, Tq, H, eps), Tq a
     multiple of K.EXTEND_TILE -> x2, row b*Tq + j at position cache.lens[b] + j.  The attention appends the new k, v rows
-    to ``cache`` layer ``layer`` and then runs K.attn_extend over the cache; the linears are BL.linear_fwd.  No host
-    read-back; cache.lens unchanged."""
+    to ``cache`` layer ``layer`` and then runs K.attn_extend over the cache; the linears are BL.linear_fwd, or
+    BL.linear_fwd_wq on ``shadows`` in a stored form of ops/quant.py, as in :func:`block_prefill`.  No host read-back;
+    cache.lens unchanged."""
     B, Tq, H, eps = conf[:4]
     need_fused_kernels(x.shape[1], H)
     if Tq % K.EXTEND_TILE or x.shape[0] != B * Tq or cache.B != B:
@@ -622,7 +625,7 @@ def block_extend(x, conf, shadows, params, cache, layer):
     def attn(qkv):
         append(qkv, *cache.layer(layer), cache.lens)
         return extend(qkv, *cache.layer(layer), cache.lens, scale=1.0 / math.sqrt(x.shape[1] // H))
-    return _block_infer(x, eps, shadows, params, BL.linear_fwd, attn)
+    return _block_infer(x, eps, shadows, params, BL.linear_fwd_wq if isinstance(shadows[0], tuple) else BL.linear_fwd, attn)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -63,6 +63,9 @@ def build_parser():
     ap.add_argument("--decode-weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
                     help="fp8: the decode steps stream the block linears and the LM head as e4m3 codes with row scales; "
                          "mxfp4: as e2m1 codes with one scale per 32 elements (weight-only; GPT2.generate)")
+    ap.add_argument("--prefill-weights", choices=["bf16", "decode"], default="bf16",
+                    help="decode: the prompt (and every --chunk piece) runs on the stored --decode-weights too, one model for "
+                         "the whole call (needs --decode-weights fp8 or mxfp4; GPT2.generate)")
     ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: the key/value cache holds e4m3 codes with one scale per 64-element row (GPT2.generate)")
     ap.add_argument("--decode-fused", action="store_true",
@@ -101,7 +104,7 @@ def main(argv=None):
         raise SystemExit(f"--chunk {args.chunk}: expected a positive number of tokens")
     kw = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, eos_token=args.eos_token,
               graph=args.graph and dev.type == "cuda", decode_weights=args.decode_weights, kv_cache=args.kv_cache,
-              decode_fused=args.decode_fused, **draw)
+              decode_fused=args.decode_fused, prefill_weights=args.prefill_weights, **draw)
     idx = idx.to(dev)
     try:
         if args.chunk is not None and dev.type == "cuda":
@@ -110,8 +113,13 @@ def main(argv=None):
             cache = KVCache(model, idx.shape[0], idx.shape[1] + args.max_new_tokens + (S if S > 1 else 0), dev, S=S,
                             dtype=args.kv_cache)
             pieces = list(idx.split(args.chunk, dim=1))
+            ingest = {}
+            if args.prefill_weights == "decode" and args.decode_weights != "bf16":      # quantised once for every piece
+                from pytorch_distributed_nn_amd.generation import DecodeWeights
+                kw["decode_weights"] = DecodeWeights(model, args.decode_weights)
+                ingest = dict(decode_weights=kw["decode_weights"], prefill_weights="decode")
             for piece in pieces[:-1]:
-                model.generate(piece, 0, cache=cache, resume=True)
+                model.generate(piece, 0, cache=cache, resume=True, **ingest)
             out = model.generate(pieces[-1], args.max_new_tokens, cache=cache, resume=True, **kw)
             head = idx[:, :idx.shape[1] - pieces[-1].shape[1]]
             out = (torch.cat([head, out[0]], 1), out[1]) if args.speculate is not None else torch.cat([head, out], 1)
