@@ -6,10 +6,13 @@ S4 tf flags).  All reference flag names and defaults are accept
 
 New:  --mode ddp|ps|single (default: ps when --comm-type is Bcast/Async and world > 1, i.e. the
 reference's behaviour; ddp when --comm-type AllReduce), --comm-type AllReduce, --bucket-cap-mb,
---dtype bf16|fp32|fp8, --synthetic, --data-dir, --max-steps, --optimizer sgd|adam|adamw|lars|lamb, --weight-decay,
+--dtype bf16|fp32|fp8, --synthetic, --data-dir, --max-steps, --optimizer sgd|adam|adamw|lars|lamb|muon, --weight-decay,
 --trust-coef ETA (lars; lars and lamb scale each tensor's step by a trust ratio ||w|| / ||update|| and leave 1-D
 parameters, biases and normalisation gains, out of the scaling and out of weight decay; not in PS mode, whose master
 applies its own fused SGD / Adam, and not with --opt-overlap's per-bucket update),
+--adam-lr LR (muon: --lr, --momentum and --weight-decay drive the orthogonalised momentum update of the 2-D weights,
+AdamW at --adam-lr every other parameter: biases, gains, conv weights, and GPT-2's embeddings with the tied head;
+torch ops only, so --no-cuda),
 --grad-clip NORM (global L2 norm, fused into the optimizer step; 0 = off),
 --label-smoothing EPS and --z-loss Z (training loss only: the fused cross-entropy kernels mix the target with the
 uniform distribution and add Z * logsumexp^2; evaluation reports the plain cross-entropy),
@@ -52,10 +55,13 @@ def add_fit_args(p: argparse.ArgumentParser):
     p.add_argument("--synthetic", action="store_true")
     p.add_argument("--data-dir", type=str, default=None)
     p.add_argument("--max-steps", type=int, default=None)
-    p.add_argument("--optimizer", type=str, default="sgd", choices=["sgd", "adam", "adamw", "lars", "lamb"])
+    p.add_argument("--optimizer", type=str, default="sgd", choices=["sgd", "adam", "adamw", "lars", "lamb", "muon"])
     p.add_argument("--trust-coef", type=float, default=1e-3, metavar="ETA",
                    help="--optimizer lars: the trust coefficient eta of r = eta |w| / (|g| + wd |w| + eps)")
     p.add_argument("--weight-decay", type=float, default=0.0)
+    p.add_argument("--adam-lr", type=float, default=3e-4, metavar="LR",
+                   help="--optimizer muon (--no-cuda only): AdamW's learning rate for the parameters Muon does not "
+                        "orthogonalise")
     p.add_argument("--grad-clip", type=float, default=0.0, metavar="NORM",
                    help="clip the gradient to this global L2 norm before the update (0 = off); the fused optimizers "
                         "do it inside their step, one read of the flat gradient (optim/fused.py set_grad_clip)")
@@ -165,6 +171,8 @@ def parse_args(argv=None):
                          "bucket during the backward, before the gradient's global norm exists")
     if args.trust_coef != 1e-3 and args.optimizer != "lars":
         raise SystemExit(f"--trust-coef belongs to --optimizer lars (--optimizer {args.optimizer} has no such factor)")
+    if args.adam_lr != 3e-4 and args.optimizer != "muon":
+        raise SystemExit(f"--adam-lr belongs to --optimizer muon (--optimizer {args.optimizer} has one learning rate)")
     return args
 
 
@@ -176,7 +184,7 @@ def dropout_rates(args):
 # flags each mode does not use: given explicitly (or by a YAML config) with a non-default value they are an
 # error, never silently dropped (a PS sweep config that says "optimizer: adam" must run Adam or fail)
 _PS_IGNORED = ("graph", "straggler_mode", "resume", "watchdog_timeout", "inject_hang", "trace", "metrics",
-               "num_workers", "checkpoint_interval", "grad_clip", "opt_overlap", "trust_coef")
+               "num_workers", "checkpoint_interval", "grad_clip", "opt_overlap", "trust_coef", "adam_lr")
 _COLLECTIVE_IGNORED = ("evaluator", "eval_interval", "no_shortcircuit", "save_model_secs", "ps_workers")
 _STRAGGLER_ONLY = ("n_to_collect", "interval_ms", "num_aggregate")
 
@@ -188,7 +196,7 @@ def check_mode_flags(args, mode: str, world: int):
     bad, extra = [], []
     if mode == "ps":
         bad += [k for k in _PS_IGNORED if k in given]
-        if args.optimizer in ("lars", "lamb"):
+        if args.optimizer in ("lars", "lamb", "muon"):
             # the master applies the averaged gradient with its own fused sgd / adam / adamw (parallel/ps.py)
             extra.append(f"--optimizer {args.optimizer}")
     else:
@@ -220,7 +228,7 @@ def main(argv=None):
     from .data.datasets import DataLoader, dataset_from_args
     from .models import build_model
     from .ops import functional as OF
-    from .optim import LAMB, LARS, SGD, Adam, AdamW, flatten_module
+    from .optim import LAMB, LARS, SGD, Adam, AdamW, Muon, flatten_module
     from .parallel import runtime
     from .parallel.ddp import DistributedDataParallel
     from .trainer import Trainer
@@ -325,6 +333,13 @@ def main(argv=None):
                    trust_coef=args.trust_coef)
     elif args.optimizer == "lamb":
         opt = LAMB(params, lr=args.lr, weight_decay=args.weight_decay)
+    elif args.optimizer == "muon":
+        if dev.type == "cuda":
+            raise SystemExit("--optimizer muon has no fused kernels yet: it runs with --no-cuda only")
+        # embeddings (and with them GPT-2's tied head) are 2-D but no hidden matrices: AdamW, like every non-matrix
+        emb = {id(m.weight) for m in model.modules() if isinstance(m, torch.nn.Embedding)}
+        opt = Muon(params, lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay, adam_lr=args.adam_lr,
+                   exclude=lambda p: p.ndim != 2 or id(p) in emb)
     else:
         opt = AdamW(params, lr=args.lr, weight_decay=args.weight_decay)
     if isinstance(net, DistributedDataParallel):

@@ -577,4 +577,98 @@ class LAMB(_MomentsRule, _LayerwiseBase):
         return r, wn, un
 
 
-__all__ = ["SGD", "Adam", "AdamW", "LARS", "LAMB", "FlatParams"]
+# ------------------------------------------------------------------------------------------------------ Muon
+NS_COEF = (3.4445, -4.7750, 2.0315)
+
+
+def newton_schulz(x0, s, steps):
+    """The iteration of Muon in torch ops: ``x0`` bf16 [.., m, n] (Muon passes the short side as m; any shape works),
+    ``s`` = 1 / (|x0|_F + eps) (float or fp32 tensor).  fp32 matmuls of the bf16 values, rounded to bf16 at
+    the three store points; the normalisation enters the first iteration only, as s^2 on the gram and s on the update:
+
+        A = bf16(al X X^T)      B = bf16(c A A + b A)      X = bf16(o (a X + B X)),     (al, o) = (s s, s), then (1, 1)
+    """
+    a, b, c = NS_COEF
+    bf, x = torch.bfloat16, x0
+    for it in range(steps):
+        al, o = (s * s, s) if it == 0 else (1.0, 1.0)
+        xf = x.float()
+        af = (al * (xf @ xf.mT)).to(bf).float()
+        bm = (c * (af @ af) + b * af).to(bf).float()
+        x = (o * (a * xf + bm @ xf)).to(bf)
+    return x
+
+
+def _exclude_non_matrix(p):
+    """The default ``exclude`` of Muon: everything that is not a 2-D weight."""
+    return p.ndim != 2
+
+
+class Muon(_MomentsRule, _FusedBase):
+    """Muon (Jordan et al. 2024): SGD momentum whose update of every hidden weight matrix is orthogonalised by
+    ``ns_steps`` Newton-Schulz iterations in bf16 (:func:`newton_schulz`); every other parameter gets AdamW.
+
+        buf = momentum buf + g;   u = g + momentum buf (Nesterov) or buf      (g as the update sees it: scaled, clipped)
+        X = newton_schulz(bf16(u) as [min side][max side], 1 / (|u|_F + eps), ns_steps)
+        W = W (1 - lr weight_decay) - lr sqrt(max(1, rows / cols)) X
+
+    ``exclude(p)`` -> True hands a parameter to AdamW (``adam_lr``, ``adam_betas``, ``adam_eps``,
+    ``adam_weight_decay``); anything that is not 2-D always is (a 4-D conv weight too).  Embeddings and a language
+    model's head are 2-D but should be excluded by the caller.  ``exp_avg`` holds the momentum of a matrix and Adam's
+    first moment of anything else.  This is the rule in torch ops, per parameter: CPU arenas and loose tensors.  There
+    are no fused kernels for it, so a group on a GPU arena is refused (no quiet fall-back to torch ops on the arena).
+    ``ortho(gi)`` returns the last step's orthogonalised updates."""
+
+    def __init__(self, params, lr=0.02, momentum=0.95, nesterov=True, ns_steps=5, weight_decay=0.0, eps=1e-7,
+                 adam_lr=3e-4, adam_betas=(0.9, 0.999), adam_eps=1e-8, adam_weight_decay=0.0,
+                 exclude=_exclude_non_matrix):
+        if ns_steps < 1:
+            raise ValueError("Muon: ns_steps must be at least 1")
+        super().__init__(params, dict(lr=lr, momentum=momentum, nesterov=nesterov, ns_steps=ns_steps,
+                                      weight_decay=weight_decay, eps=eps, adam_lr=adam_lr, adam_betas=adam_betas,
+                                      adam_eps=adam_eps, adam_weight_decay=adam_weight_decay))
+        self._exclude = exclude
+        self._ortho_loose = {}         # parameter -> X of the last step
+
+    def _excluded(self, p):
+        return p.ndim != 2 or (self._exclude is not None and bool(self._exclude(p)))
+
+    def _overlap_ok(self):             # a bucket holds parts of matrices
+        return None
+
+    def _begin_ranges(self, gi, group):
+        raise RuntimeError("Muon has no fused kernels: a param group on a GPU arena is not supported (CPU arenas and "
+                           "loose tensors run the rule in torch ops)")
+
+    def _check_graphable(self, gi):
+        self._begin_ranges(gi, self.param_groups[gi])
+
+    def _step_param(self, group, p, gsd):
+        g = self._scaled_grad(p, gsd)
+        if self._excluded(p):
+            lr = group["adam_lr"]
+            p.mul_(1 - lr * group["adam_weight_decay"])
+            m, denom, bc1 = self._moments(dict(betas=group["adam_betas"], eps=group["adam_eps"]), p, g)
+            p.addcdiv_(m, denom, value=-lr / bc1)
+            return
+        st = self.state[p]
+        if "exp_avg" not in st:
+            st["exp_avg"] = torch.zeros_like(p)
+        mom, (rows, cols) = group["momentum"], p.shape
+        buf = st["exp_avg"].mul_(mom).add_(g)
+        u = g.add(buf, alpha=mom) if group["nesterov"] else buf
+        scale = (1.0 / (torch.linalg.vector_norm(u.double()) + group["eps"])).float()
+        x0 = u.to(torch.bfloat16)
+        x = newton_schulz(x0.t() if rows > cols else x0, scale, group["ns_steps"])
+        self._ortho_loose[p] = x
+        xw = (x.t() if rows > cols else x).float()
+        p.mul_(1 - group["lr"] * group["weight_decay"]).add_(xw, alpha=-group["lr"] * math.sqrt(max(1.0, rows / cols)))
+
+    def ortho(self, gi: int = 0):
+        """The last step's orthogonalised update of every matrix parameter of group ``gi``, in group order
+        ([min side][max side], bf16).  None before a step."""
+        mats = [p for p in self.param_groups[gi]["params"] if not self._excluded(p)]
+        return [self._ortho_loose[p] for p in mats] if all(p in self._ortho_loose for p in mats) else None
+
+
+__all__ = ["SGD", "Adam", "AdamW", "LARS", "LAMB", "Muon", "newton_schulz", "FlatParams"]
