@@ -157,6 +157,8 @@ _SIGS = {
     "pdnn_attn_softmax_bwd": [P, L, P, L, P, L, I, I, F, I, P],
     "pdnn_flash_attn_fwd": [P, P, P, I, I, I, F, I, P, P, F, P, I, P],
     "pdnn_flash_attn_bwd": [P, P, P, P, P, P, I, I, I, F, I, P, P, F, P, I, P],
+    "pdnn_flash_attn_hd128_fwd": [P, P, P, I, I, I, F, I, P],
+    "pdnn_flash_attn_hd128_bwd": [P, P, P, P, P, P, I, I, I, F, I, P],
     "pdnn_doc_bounds": [P, ctypes.c_longlong, P, P, I, I, P],
     "pdnn_attn_decode": [P, P, P, P, P, P, I, I, I, I, F, P],
     "pdnn_attn_decode_ws": [I, I, I, I],

@@ -1651,11 +1651,15 @@ def _doc_chk(name, doc_start, doc_end, B, T, dev):
 
 
 def _flash_chk(name, qkv, B, T, H, causal, doc, drop):
-    """The checks flash_attn_fwd / _bwd share -> (doc_start, doc_end, p, state, site) as the C entries take them."""
+    """The checks flash_attn_fwd / _bwd share -> head dim d (64 or 128, from qkv's width) and (doc_start, doc_end, p,
+    state, site) as the d = 64 C entries take them."""
     _bf16_c(qkv, f"{name}.qkv")
-    _chk(B >= 1 and T >= 1 and H >= 1 and qkv.shape == (B * T, 3 * H * 64) and T % 128 == 0,
-         f"{name}: qkv {tuple(qkv.shape)} B={B} T={T} H={H}")
+    d = qkv.shape[1] // (3 * H) if qkv.dim() == 2 and H >= 1 else 0
+    _chk(B >= 1 and T >= 1 and H >= 1 and d in (64, 128) and qkv.shape == (B * T, 3 * H * d) and T % 128 == 0,
+         f"{name}: qkv {tuple(qkv.shape)} B={B} T={T} H={H} (head dim 64 or 128, T % 128 == 0)")
     _chk(causal or (doc is None and drop is None), f"{name}: doc and drop exist under the causal mask only")
+    _chk(d == 64 or (doc is None and drop is None),
+         f"{name}: the head-dim-128 kernels have neither a document mask nor dropout (head dim 64 has both)")
     ds = de = state = None
     p, site = 0.0, 0
     if doc is not None:
@@ -1667,14 +1671,14 @@ def _flash_chk(name, qkv, B, T, H, causal, doc, drop):
         p, state, site = drop
         p = _drop_chk(name, p, state, site, qkv.device)
         _chk(p == 0.0 or T <= 65536, f"{name}: dropout needs T <= 65536, got T={T}")
-    return ptr(ds), ptr(de), p, ptr(state), site
+    return d, (ptr(ds), ptr(de), p, ptr(state), site)
 
 
-def _flash_bwd_chk(name, out, dout, lse2, B, T, H):
+def _flash_bwd_chk(name, out, dout, lse2, B, T, H, d):
     """The forward's results and the incoming gradient of flash_attn_bwd -> dout, contiguous."""
     dout = dout.contiguous()
-    _chk(out.dtype == BF16 and out.shape == (B * T, H * 64) and out.is_contiguous(),
-         f"{name}: out must be contiguous bf16 [B*T][H*64]")
+    _chk(out.dtype == BF16 and out.shape == (B * T, H * d) and out.is_contiguous(),
+         f"{name}: out must be contiguous bf16 [B*T][H*{d}]")
     _chk(dout.dtype == BF16 and dout.shape == out.shape, f"{name}: dout must be bf16 of out's shape")
     _chk(lse2.dtype == F32 and lse2.shape == (B, H, T) and lse2.is_contiguous(),
          f"{name}: lse2 must be contiguous fp32 [B][H][T]")
@@ -1682,26 +1686,34 @@ def _flash_bwd_chk(name, out, dout, lse2, B, T, H):
 
 
 def flash_attn_fwd(qkv, B, T, H, scale, causal=True, *, doc=None, drop=None):
-    """Fused attention, head dim 64: qkv [B*T][3*H*64] -> (out [B*T][H*64], lse2 [B][H][T]).
+    """Fused attention, head dim d = 64 or 128 (taken from qkv's width): qkv [B*T][3*H*d] -> (out [B*T][H*d], lse2
+    [B][H][T]).  d = 128 runs the kernels of csrc/kernels/attention_hd128.hip, which take neither ``doc`` nor ``drop``.
     ``doc`` = (doc_start, doc_end), bounds as from :func:`doc_bounds`: the causal packed-document mask, query q of
     sequence b sees key k iff doc_start[b][q] <= k <= q.
     ``drop`` = (p, state, site): dropout ``p`` on the probabilities, O = (P o keep) V / (1 - p_eff); lse2 is that of the
     undropped softmax.  p == 0 runs the kernels without dropout.  Both need ``causal``."""
-    masks = _flash_chk("flash_attn", qkv, B, T, H, causal, doc, drop)
-    out = torch.empty(B * T, H * 64, device=qkv.device, dtype=BF16)
+    d, masks = _flash_chk("flash_attn", qkv, B, T, H, causal, doc, drop)
+    out = torch.empty(B * T, H * d, device=qkv.device, dtype=BF16)
     lse2 = torch.empty(B, H, T, device=qkv.device, dtype=F32)
-    call("pdnn_flash_attn_fwd", ptr(qkv), ptr(out), ptr(lse2), B, T, H, float(scale), int(causal), *masks, stream())
+    if d == 128:
+        call("pdnn_flash_attn_hd128_fwd", ptr(qkv), ptr(out), ptr(lse2), B, T, H, float(scale), int(causal), stream())
+    else:
+        call("pdnn_flash_attn_fwd", ptr(qkv), ptr(out), ptr(lse2), B, T, H, float(scale), int(causal), *masks, stream())
     return out, lse2
 
 
 def flash_attn_bwd(qkv, out, dout, lse2, B, T, H, scale, causal=True, *, doc=None, drop=None):
     """dqkv of :func:`flash_attn_fwd` from its results and ``dout``; causal, doc and drop as the forward had them."""
-    masks = _flash_chk("flash_attn_bwd", qkv, B, T, H, causal, doc, drop)
-    dout = _flash_bwd_chk("flash_attn_bwd", out, dout, lse2, B, T, H)
+    d, masks = _flash_chk("flash_attn_bwd", qkv, B, T, H, causal, doc, drop)
+    dout = _flash_bwd_chk("flash_attn_bwd", out, dout, lse2, B, T, H, d)
     dqkv = torch.empty_like(qkv)
     delta = torch.empty(B, H, T, device=qkv.device, dtype=F32)
-    call("pdnn_flash_attn_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse2), ptr(delta), ptr(dqkv), B, T, H, float(scale),
-         int(causal), *masks, stream())
+    if d == 128:
+        call("pdnn_flash_attn_hd128_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse2), ptr(delta), ptr(dqkv), B, T, H,
+             float(scale), int(causal), stream())
+    else:
+        call("pdnn_flash_attn_bwd", ptr(qkv), ptr(out), ptr(dout), ptr(lse2), ptr(delta), ptr(dqkv), B, T, H, float(scale),
+             int(causal), *masks, stream())
     return dqkv
 
 

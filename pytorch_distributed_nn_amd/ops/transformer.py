@@ -18,9 +18,9 @@ forward                                              backward
   x2  = x1 + h Wfc2^T + b     gemm_nt_ex(res=x1)       dx   = LN1_bwd(dln1) + dx1
 
 The residual stream is bf16 [B*T][D]; LayerNorm statistics, GEMM accumulation, softmax and all weight
-gradients are fp32.  Attention (head dim 64, T % 128 == 0) runs the fused flash kernels of
-``csrc/kernels/attention.hip`` (scores never leave registers; backward recomputes P from the saved
-log-sum-exp); other shapes fall back to the materialised path below (batched MFMA GEMMs with causal tile
+gradients are fp32.  Attention (head dim 64 or 128, T % 128 == 0) runs the fused flash kernels of
+``csrc/kernels/attention.hip`` / ``attention_hd128.hip`` (scores never leave registers; backward recomputes P from the
+saved log-sum-exp; the document mask and attention dropout exist at head dim 64 only); other shapes fall back to the materialised path below (batched MFMA GEMMs with causal tile
 skipping + row-softmax kernels).
 """
 from __future__ import annotations
@@ -95,7 +95,7 @@ def attention_bwd(dy, qkv, P, B, T, H, causal=True, dS_buf=None):
 
 
 def use_flash(T, D, H):
-    return D // H == 64 and T % 128 == 0
+    return D % H == 0 and D // H in (64, 128) and T % 128 == 0
 
 
 def attention_reference(qkv, B, T, H, causal=True, mask=None):
@@ -391,6 +391,10 @@ class _BlockAttn:
         if self.drop is not None and not self.flash:
             raise ValueError(f"attention dropout needs the fused kernels (head dim 64, T % 128 == 0); got head dim "
                              f"{D // H}, T = {T}: the unfused attention chain has no dropout (attn_pdrop = 0 runs it)")
+        if D // H == 128 and (self.doc is not None or self.drop is not None):
+            raise ValueError(f"packed-document attention and attention dropout need head dim 64; got head dim 128, T = "
+                             f"{T}: the head-dim-128 flash kernels have neither, and the unfused attention chain has "
+                             f"neither")
 
     def fwd(self, qkv):
         """-> y, P, S: P is lse2 and S None on the flash kernels; the chain's S is the backward's fp32 dP scratch"""
