@@ -67,6 +67,8 @@ KERNEL_FILE_FLAGS["gemm_wq.hip"] = NO_PK_F32
 # attention_hd128.hip: attention.hip's mix of MFMA results and VALU work, and new code (its header's register counts were
 # taken with both)
 KERNEL_FILE_FLAGS["attention_hd128.hip"] = VGPR_FORM + NO_PK_F32
+# attention_decode_hd128.hip: new code, the same rule (its header's register counts were taken with it); no MFMA in it
+KERNEL_FILE_FLAGS["attention_decode_hd128.hip"] = NO_PK_F32
 CXX_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-Wall", "-Wextra", "-Wno-unused-parameter",
              "-pthread", f"-I{ROOT / 'csrc' / 'include'}", f"-I{ROOT / 'csrc' / 'runtime'}"]
 

@@ -161,6 +161,8 @@ def check_args(c, idx, max_new_tokens, *, temperature, top_k, eos_token, prompt_
     have = getattr(cache, "dtype", None)                # None: the cache follows a passed cache=, else it is bf16
     if kv_cache is not None and have is not None and have != kv_cache:
         raise ValueError(f"generate: kv_cache={kv_cache!r} with a cache= of dtype {have!r}")
+    if idx.is_cuda and (kv_cache or have) == "fp8":
+        TX.need_head_dim_64(c.n_embd // c.n_head, "generate: kv_cache='fp8'")
     if decode_fused and idx.is_cuda and (not tuning.get("decode_skinny") or B * (S or 1) > K.FUSED_ROWS
                                          or c.n_embd % 8 or c.n_embd > K.FUSED_MAX_D):
         raise ValueError(f"generate: decode_fused on the GPU needs tuning decode_skinny on, B * speculate <= "
@@ -185,6 +187,7 @@ def check_resume(c, idx, B, pl, N, S, cache):
     if cache.k.device != idx.device or (S or 1) > cache.S:
         raise ValueError(f"generate: resume=True with a cache of S = {cache.S} on {cache.k.device}, need S >= {S or 1} on "
                          f"{idx.device}")
+    TX.need_head_dim_64(c.n_embd // c.n_head, "generate: resume=True")
     room, extra = min(c.block_size, cache.Tmax), N + (S or 0)
     for b, (have, new) in enumerate(zip(cache.lens.tolist(), pl)):
         if have < 0 or have + new + extra > room:
@@ -538,6 +541,9 @@ class Session:
         self.model, self.B, self.max_len = model, B, max_len
         self.device = model.transformer.wte.weight.device
         self.history, self.cached = [[] for _ in range(B)], [0] * B
+        if self.device.type == "cuda":                  # every turn is a resume=True call
+            TX.need_fused_kernels(model.config.n_embd, model.config.n_head)
+            TX.need_head_dim_64(model.config.n_embd // model.config.n_head, "session: a session on the GPU")
         self.cache = TX.KVCache(model, B, max_len, self.device, S=S, dtype=kv_cache) if self.device.type == "cuda" else None
         # quantised once, here: every turn runs on this snapshot of the weights
         self.sampling = {"decode_weights": DecodeWeights(model, decode_weights)} if decode_weights != "bf16" else {}

@@ -27,7 +27,8 @@ and not in ``state_dict``.  The CPU path applies the same bits (``ops.transforme
 
 Generation (``generate``, a delegate to ``generation.py``): one prefill over the prompt, then one single-token step per
 new token against a key/value cache (GPU: ``ops.transformer.KVCache`` / ``block_prefill`` / ``block_step``, head dim 64
-only; CPU: a plain fp32 cache, the reference of the GPU path).  The document mask is not applied there.
+or 128, the latter without ``resume``, sessions and ``kv_cache="fp8"``; CPU: a plain fp32 cache, the reference of the GPU
+path).  The document mask is not applied there.
 """
 from __future__ import annotations
 

@@ -164,6 +164,11 @@ _SIGS = {
     "pdnn_attn_decode_ws": [I, I, I, I],
     "pdnn_attn_decode_multi": [P, P, P, P, P, P, I, I, I, I, I, F, P],
     "pdnn_attn_decode_multi_ws": [I, I, I, I, I],
+    "pdnn_attn_decode_hd128": [P, P, P, P, P, P, I, I, I, I, F, P],
+    "pdnn_attn_decode_hd128_ws": [I, I, I, I],
+    "pdnn_attn_decode_multi_hd128": [P, P, P, P, P, P, I, I, I, I, I, F, P],
+    "pdnn_attn_decode_multi_hd128_ws": [I, I, I, I, I],
+    "pdnn_kv_cache_fill_hd128": [P, P, P, I, I, I, I, P],
     "pdnn_spec_prepare": [P, I, I, I, P, P, P, ctypes.c_longlong, P, I, I, I, P, P, P, P],
     "pdnn_spec_accept": [P, P, P, I, I, I, P, P, P, ctypes.c_longlong, P, P, I, I, P],
     "pdnn_kv_cache_fill": [P, P, P, I, I, I, I, P],

@@ -8,6 +8,7 @@ allocator, and launches on torch's current stream.  Activations are NHWC bf16 te
 from __future__ import annotations
 
 import ctypes
+import math
 
 import torch
 
@@ -1717,23 +1718,26 @@ def flash_attn_bwd(qkv, out, dout, lse2, B, T, H, scale, causal=True, *, doc=Non
     return dqkv
 
 
-# ----------------------------------------------------------------------------------- decode attention (attention_decode.hip)
+# ----------------------------------------------------------------------------------- decode attention (attention_decode.hip, attention_decode_hd128.hip)
 DECODE_CHUNK = 128          # keys per block of the split; profiles/attention_decode.txt holds the sweep that picked it
 DECODE_CHUNKS = (64, 128, 256)
 
 
-def _cache_chk(name, kcache, vcache, dev, scales=None):
-    """``scales`` = (kscale, vscale): the fp8 cache, uint8 codes with fp32 [B][H][Tmax] row scales"""
+def _cache_chk(name, kcache, vcache, dev, scales=None, dims=(64,)):
+    """-> the head dim d, the cache's last dimension, one of ``dims`` (128: attention_decode_hd128.hip, which has the bf16
+    fill and decode kernels only).  ``scales`` = (kscale, vscale): the fp8 cache, uint8 codes with fp32 [B][H][Tmax] row
+    scales"""
     dtype, dname = (BF16, "bf16") if scales is None else (torch.uint8, "uint8")
     for t, what in ((kcache, "kcache"), (vcache, "vcache")):
-        _chk(torch.is_tensor(t) and t.dtype == dtype and t.is_cuda and t.dim() == 4 and t.shape[3] == 64
+        _chk(torch.is_tensor(t) and t.dtype == dtype and t.is_cuda and t.dim() == 4 and t.shape[3] in dims
              and t.is_contiguous() and t.device == dev and t.data_ptr() % 16 == 0,
-             f"{name}: {what} must be contiguous CUDA {dname} [B][H][Tmax][64] on {dev}")
+             f"{name}: {what} must be contiguous CUDA {dname} [B][H][Tmax][{' or '.join(map(str, dims))}] on {dev}")
     _chk(kcache.shape == vcache.shape and min(kcache.shape) >= 1,
          f"{name}: kcache {tuple(kcache.shape)} and vcache {tuple(vcache.shape)} must have one non-empty shape")
     for t, what in zip(scales or (), ("kscale", "vscale")):
         _chk(torch.is_tensor(t) and t.dtype == F32 and t.shape == kcache.shape[:3] and t.is_contiguous() and t.device == dev,
              f"{name}: {what} must be contiguous CUDA fp32 {tuple(kcache.shape[:3])} on {dev}")
+    return kcache.shape[3]
 
 
 def _attn_decode(name, sym, S, qkv, kcache, vcache, lens, chunk, out, part, scale, scales=None):
@@ -1742,65 +1746,70 @@ def _attn_decode(name, sym, S, qkv, kcache, vcache, lens, chunk, out, part, scal
     _bf16_c(qkv, f"{name}.qkv")
     _chk(isinstance(chunk, int) and chunk in DECODE_CHUNKS, f"{name}: chunk must be one of {DECODE_CHUNKS}, got {chunk!r}")
     _chk(S is None or (isinstance(S, int) and 1 <= S <= DECODE_MAX_S), f"{name}: 1 <= S <= {DECODE_MAX_S}, got S = {S!r}")
-    _cache_chk(name, kcache, vcache, qkv.device, scales)
+    d = _cache_chk(name, kcache, vcache, qkv.device, scales, (64,) if scales else (64, 128))
     B, H, Tmax, _ = kcache.shape
     if S is None:
-        R, per, want = B, (), f"B={B} H={H}: expected [B][3*H*64]"
+        R, per, want = B, (), f"B={B} H={H}: expected [B][3*H*{d}]"
     else:
-        R, per, want = B * S, (S,), f"B={B} S={S} H={H}: expected [B*S][3*H*64]"
-    _chk(qkv.shape == (R, 3 * H * 64), f"{name}: qkv {tuple(qkv.shape)} for {want}")
+        R, per, want = B * S, (S,), f"B={B} S={S} H={H}: expected [B*S][3*H*{d}]"
+    _chk(qkv.shape == (R, 3 * H * d), f"{name}: qkv {tuple(qkv.shape)} for {want}")
     _chk(torch.is_tensor(lens) and lens.dtype == torch.int32 and lens.shape == (B,) and lens.is_contiguous()
          and lens.device == qkv.device, f"{name}: lens must be contiguous int32 [{B}] on {qkv.device}")
-    ws = attn_decode_ws(B, H, Tmax, chunk) if S is None else attn_decode_multi_ws(B, S, H, Tmax, chunk)
+    ws = attn_decode_ws(B, H, Tmax, chunk, d=d) if S is None else attn_decode_multi_ws(B, S, H, Tmax, chunk, d=d)
     if out is None:
-        out = torch.empty(R, H * 64, device=qkv.device, dtype=BF16)
+        out = torch.empty(R, H * d, device=qkv.device, dtype=BF16)
     else:
-        _chk(out.dtype == BF16 and out.shape == (R, H * 64) and out.is_contiguous() and out.device == qkv.device,
-             f"{name}: out must be contiguous bf16 [{R}][{H * 64}] on {qkv.device}")
+        _chk(out.dtype == BF16 and out.shape == (R, H * d) and out.is_contiguous() and out.device == qkv.device,
+             f"{name}: out must be contiguous bf16 [{R}][{H * d}] on {qkv.device}")
     if part is None:
         part = torch.empty(ws, device=qkv.device, dtype=F32)
     else:
         _chk(part.dtype == F32 and part.is_contiguous() and part.numel() >= ws and part.device == qkv.device,
              f"{name}: part must be contiguous fp32 with >= {ws} elements on {qkv.device}")
-    call(sym, ptr(qkv), ptr(kcache), ptr(vcache), *map(ptr, scales or ()), ptr(lens), ptr(out), ptr(part), B, *per, H, Tmax,
-         chunk, float(0.125 if scale is None else scale), stream())
+    call(sym + _HD128[d], ptr(qkv), ptr(kcache), ptr(vcache), *map(ptr, scales or ()), ptr(lens), ptr(out), ptr(part), B,
+         *per, H, Tmax, chunk, float(1.0 / math.sqrt(d) if scale is None else scale), stream())
     return out
 
 
-def attn_decode_ws(B, H, Tmax, chunk=DECODE_CHUNK):
-    """fp32 elements of the ``part`` scratch of :func:`attn_decode`"""
+_HD128 = {64: "", 128: "_hd128"}    # head dim -> suffix of the C entry (attention_decode.hip, attention_decode_hd128.hip)
+
+
+def attn_decode_ws(B, H, Tmax, chunk=DECODE_CHUNK, d=64):
+    """fp32 elements of the ``part`` scratch of :func:`attn_decode` at head dim ``d``"""
     _chk(chunk in DECODE_CHUNKS, f"attn_decode: chunk must be one of {DECODE_CHUNKS}, got {chunk!r}")
-    n = lib().pdnn_attn_decode_ws(B, H, Tmax, chunk)
+    _chk(d in _HD128, f"attn_decode: head dim must be 64 or 128, got {d!r}")
+    n = getattr(lib(), f"pdnn_attn_decode{_HD128[d]}_ws")(B, H, Tmax, chunk)
     _chk(n > 0, f"attn_decode: B={B} H={H} Tmax={Tmax} chunk={chunk}")
     return n
 
 
 def attn_decode(qkv, kcache, vcache, lens, chunk=DECODE_CHUNK, out=None, part=None, scale=None):
-    """One new token per sequence against the cache, head dim 64: qkv bf16 [B][3*H*64] (packed as for flash_attn_fwd),
-    kcache / vcache bf16 [B][H][Tmax][64], lens int32 [B] on the device (tokens already cached; read by the kernel only).
-    Stores the new k, v rows into slot lens[b] and returns out bf16 [B][H*64] = softmax over keys 0..lens[b] times V.
-    ``lens`` is not changed.  ``out`` / ``part`` (fp32, >= attn_decode_ws elements): preallocated buffers, so that a
-    captured step allocates nothing.  ``scale`` defaults to 1 / 8."""
+    """One new token per sequence against the cache, head dim d = 64 or 128 (the cache's last dimension): qkv bf16
+    [B][3*H*d] (packed as for flash_attn_fwd), kcache / vcache bf16 [B][H][Tmax][d], lens int32 [B] on the device (tokens
+    already cached; read by the kernel only).  Stores the new k, v rows into slot lens[b] and returns out bf16 [B][H*d] =
+    softmax over keys 0..lens[b] times V.  ``lens`` is not changed.  ``out`` / ``part`` (fp32, >= attn_decode_ws(d=d)
+    elements): preallocated buffers, so that a captured step allocates nothing.  ``scale`` defaults to 1 / sqrt(d)."""
     return _attn_decode("attn_decode", "pdnn_attn_decode", None, qkv, kcache, vcache, lens, chunk, out, part, scale)
 
 
 DECODE_MAX_S = 8            # most queries per sequence of attn_decode_multi
 
 
-def attn_decode_multi_ws(B, S, H, Tmax, chunk=DECODE_CHUNK):
-    """fp32 elements of the ``part`` scratch of :func:`attn_decode_multi`"""
+def attn_decode_multi_ws(B, S, H, Tmax, chunk=DECODE_CHUNK, d=64):
+    """fp32 elements of the ``part`` scratch of :func:`attn_decode_multi` at head dim ``d``"""
     _chk(chunk in DECODE_CHUNKS, f"attn_decode_multi: chunk must be one of {DECODE_CHUNKS}, got {chunk!r}")
     _chk(isinstance(S, int) and 1 <= S <= DECODE_MAX_S, f"attn_decode_multi: 1 <= S <= {DECODE_MAX_S}, got S = {S!r}")
-    n = lib().pdnn_attn_decode_multi_ws(B, S, H, Tmax, chunk)
+    _chk(d in _HD128, f"attn_decode_multi: head dim must be 64 or 128, got {d!r}")
+    n = getattr(lib(), f"pdnn_attn_decode_multi{_HD128[d]}_ws")(B, S, H, Tmax, chunk)
     _chk(n > 0, f"attn_decode_multi: B={B} S={S} H={H} Tmax={Tmax} chunk={chunk}")
     return n
 
 
 def attn_decode_multi(qkv, kcache, vcache, lens, S, chunk=DECODE_CHUNK, out=None, part=None, scale=None):
-    """``S`` new tokens per sequence against the cache in one call (1 <= S <= 8), head dim 64: qkv bf16 [B*S][3*H*64],
-    row b*S + j the query at position lens[b] + j, which sees the cache keys 0..lens[b]-1 and the new keys of rows b*S ..
-    b*S+j.  Stores the S new k, v rows into slots lens[b]..lens[b]+S-1 and returns out bf16 [B*S][H*64]; ``lens`` is not
-    changed.  Bit for bit what S successive :func:`attn_decode` calls give with lens advanced by one between them.
+    """``S`` new tokens per sequence against the cache in one call (1 <= S <= 8), head dim d = 64 or 128 (the cache's last
+    dimension): qkv bf16 [B*S][3*H*d], row b*S + j the query at position lens[b] + j, which sees the cache keys
+    0..lens[b]-1 and the new keys of rows b*S .. b*S+j.  Stores the S new k, v rows into slots lens[b]..lens[b]+S-1 and
+    returns out bf16 [B*S][H*d]; ``lens`` is not changed.  Bit for bit what S successive :func:`attn_decode` calls give with lens advanced by one between them.
     ``out`` / ``part`` (fp32, >= attn_decode_multi_ws elements) and ``scale`` as for :func:`attn_decode`."""
     return _attn_decode("attn_decode_multi", "pdnn_attn_decode_multi", S, qkv, kcache, vcache, lens, chunk, out, part,
                         scale)
@@ -1858,14 +1867,14 @@ def spec_accept(tok_in, t, out, P, N, ntok, lens, done, stats, S, finished=None,
 
 
 def kv_cache_fill(qkv, kcache, vcache, B, T):
-    """Prefill: the K and V columns of qkv bf16 [B*T][3*H*64] into slots 0..T-1 of kcache / vcache bf16 [B][H][Tmax][64]
-    (T <= Tmax; slots >= T are untouched)."""
+    """Prefill: the K and V columns of qkv bf16 [B*T][3*H*d] into slots 0..T-1 of kcache / vcache bf16 [B][H][Tmax][d],
+    d = 64 or 128 (T <= Tmax; slots >= T are untouched)."""
     _bf16_c(qkv, "kv_cache_fill.qkv")
-    _cache_chk("kv_cache_fill", kcache, vcache, qkv.device)
+    d = _cache_chk("kv_cache_fill", kcache, vcache, qkv.device, dims=(64, 128))
     Bc, H, Tmax, _ = kcache.shape
-    _chk(B == Bc and 1 <= T <= Tmax and qkv.shape == (B * T, 3 * H * 64),
+    _chk(B == Bc and 1 <= T <= Tmax and qkv.shape == (B * T, 3 * H * d),
          f"kv_cache_fill: qkv {tuple(qkv.shape)} B={B} T={T} for a cache {tuple(kcache.shape)}")
-    call("pdnn_kv_cache_fill", ptr(qkv), ptr(kcache), ptr(vcache), B, T, H, Tmax, stream())
+    call("pdnn_kv_cache_fill" + _HD128[d], ptr(qkv), ptr(kcache), ptr(vcache), B, T, H, Tmax, stream())
 
 
 # ----------------------------------------------------------------------------------- extend attention (attention_extend.hip)

@@ -22,6 +22,10 @@ gradients are fp32.  Attention (head dim 64 or 128, T % 128 == 0) runs the fused
 ``csrc/kernels/attention.hip`` / ``attention_hd128.hip`` (scores never leave registers; backward recomputes P from the
 saved log-sum-exp; the document mask and attention dropout exist at head dim 64 only); other shapes fall back to the materialised path below (batched MFMA GEMMs with causal tile
 skipping + row-softmax kernels).
+
+Inference (:class:`KVCache`, :func:`block_prefill`, :func:`block_step`) runs at head dim 64 and 128
+(``csrc/kernels/attention_decode.hip`` / ``attention_decode_hd128.hip``); :func:`block_extend` and the fp8 cache exist at
+head dim 64 only and refuse 128.
 """
 from __future__ import annotations
 
@@ -488,8 +492,9 @@ class GPT2BlockFn(torch.autograd.Function):
 # inference: key/value cache, prefill and decode-step blocks (plain functions, no autograd)
 # ------------------------------------------------------------------------------------------------
 class KVCache:
-    """The key/value cache of one generation batch on the GPU (csrc/kernels/attention_decode.hip): one K and one V
-    allocation bf16 [L][B][H][Tmax][64], ``lens`` int32 [B] on the device (tokens of sequence b already cached; the
+    """The key/value cache of one generation batch on the GPU (csrc/kernels/attention_decode.hip, and
+    attention_decode_hd128.hip at head dim 128, bf16 only): one K and one V allocation bf16 [L][B][H][Tmax][hd], hd = 64
+    or 128, ``lens`` int32 [B] on the device (tokens of sequence b already cached; the
     decode kernels read it there, the host never does) and the fp32 scratch of the split decode kernel, sized for ``S``
     queries per sequence (S > 1: :func:`block_step`).  Slots at or past lens[b] may hold anything, so :meth:`reset`
     only zeroes ``lens``.  ``dtype="fp8"`` (csrc/kernels/attention_cache_fp8.hip): ``k``, ``v`` are uint8 e4m3fn codes of
@@ -501,6 +506,9 @@ class KVCache:
         if dtype not in ("bf16", "fp8"):
             raise ValueError(f"KVCache: dtype must be 'bf16' or 'fp8', got {dtype!r}")
         need_fused_kernels(c.n_embd, c.n_head)
+        hd = c.n_embd // c.n_head
+        if dtype == "fp8":
+            need_head_dim_64(hd, "KVCache(dtype='fp8')")
         if B < 1 or Tmax < 1:
             raise ValueError(f"KVCache: B = {B}, Tmax = {Tmax}")
         if not (isinstance(S, int) and 1 <= S <= K.DECODE_MAX_S):
@@ -508,13 +516,13 @@ class KVCache:
         self.B, self.H, self.Tmax, self.L, self.S = B, c.n_head, Tmax, c.n_layer, S
         self.chunk = K.DECODE_CHUNK if chunk is None else chunk
         self.dtype = dtype
-        self.k = torch.zeros(c.n_layer, B, c.n_head, Tmax, 64, device=device, dtype=BF16 if dtype == "bf16" else torch.uint8)
+        self.k = torch.zeros(c.n_layer, B, c.n_head, Tmax, hd, device=device, dtype=BF16 if dtype == "bf16" else torch.uint8)
         self.v = torch.zeros_like(self.k)
         if dtype == "fp8":
             self.ks = torch.ones(c.n_layer, B, c.n_head, Tmax, device=device, dtype=F32)
             self.vs = torch.ones_like(self.ks)
         self.lens = torch.zeros(B, device=device, dtype=torch.int32)
-        self.part = torch.empty(K.attn_decode_multi_ws(B, S, c.n_head, Tmax, self.chunk), device=device, dtype=F32)
+        self.part = torch.empty(K.attn_decode_multi_ws(B, S, c.n_head, Tmax, self.chunk, d=hd), device=device, dtype=F32)
 
     def reset(self):
         self.lens.zero_()
@@ -531,14 +539,23 @@ class KVCache:
 
 
 def need_fused_kernels(D, H, T=None):
-    """Generation runs on the head-dim-64 kernels only, a prefill (``T`` given) on the flash kernels (:func:`use_flash`)"""
+    """Generation runs on the decode attention kernels, which exist at head dims 64 and 128 only, a prefill (``T`` given) on
+    the flash kernels (:func:`use_flash`).  (The refusals keep their first words from when 64 was the only head dim.)"""
     hd = D // H
-    if hd == 64 and D % H == 0 and (T is None or T % 128 == 0):
+    if hd in (64, 128) and D % H == 0 and (T is None or T % 128 == 0):
         return
     if T is not None:
-        raise ValueError(f"generation needs the fused kernels (head dim 64, T % 128 == 0); got head dim {hd}, T = {T}")
-    raise ValueError(f"generation needs the fused kernels (head dim 64); got head dim {hd}: the decode attention kernel "
-                     f"has no other head dim (the CPU path runs any)")
+        raise ValueError(f"generation needs the fused kernels (head dim 64, T % 128 == 0); got head dim {hd}, T = {T} "
+                         f"(head dim 128 runs too)")
+    raise ValueError(f"generation needs the fused kernels (head dim 64); got head dim {hd}: the decode attention kernels "
+                     f"exist at head dims 64 and 128 only (the CPU path runs any)")
+
+
+def need_head_dim_64(hd, what):
+    """The extend / append kernels and the fp8 key/value cache exist at head dim 64 only: ``what`` at head dim 128 is refused"""
+    if hd != 64:
+        raise ValueError(f"{what} at head dim {hd}: the extend kernel and the fp8 key/value cache exist at head dim 64 only "
+                         f"(head dim 128 has the bf16 cache with prefill and decode, no resume, Session or kv_cache='fp8')")
 
 
 def _block_infer(x, eps, shadows, params, lin, attn, *args, **kw):
@@ -619,6 +636,7 @@ def block_extend(x, conf, shadows, params, cache, layer):
     cache.lens unchanged."""
     B, Tq, H, eps = conf[:4]
     need_fused_kernels(x.shape[1], H)
+    need_head_dim_64(x.shape[1] // H, "block_extend")
     if Tq % K.EXTEND_TILE or x.shape[0] != B * Tq or cache.B != B:
         raise ValueError(f"block_extend: {x.shape[0]} rows for B = {B}, Tq = {Tq} (a multiple of {K.EXTEND_TILE}), cache "
                          f"B = {cache.B}")
